@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - frames/s of the ALIKED + LightGlue hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): frames/sec ALIKED+LightGlue @1241x376.  Workload =
 config C2/C4: synthetic 1241x376x3 uint8 frames (white
@@ -18,7 +18,18 @@ CHILD process before anything touches the GPU) and relays rank 0's JSON line,
 so one command shape works for N = 1, 2, 4, 8; under torch.distributed.run it
 is one of the ranks.  At N = 1 the whole run is on the C-ABI (no torch).
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on
+rank 0: the contract fields (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...), `config`, `build` and
+  step_ms      - p10 / p50 / p90 of the per-round durations inside the timed
+                 region (timing events on a collector stream, no host sync)
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step
+computed on rank 0 as DIR/<name>.npy (float32 / float64; see dump_outputs()).
+
+--full adds everything else the benchmark measures (runs of their own after
+the timed region; --no-extras keeps only roofline + structured_input of them,
+--no-cpu-baseline drops cpu_baseline and the CPU side of `ba`):
   roofline     - the dominant kernel (LightGlue attention, split-f16 MFMA):
                  HIP events around every launch; `frac` from the launches of a
                  batch replayed on an otherwise idle GPU right after the timed
@@ -27,8 +38,7 @@ Rank 0 prints ONE JSON line with the contract fields plus
                  hipGraphs, which host-side event records cannot bracket)
   exact_f32    - the same pipeline with every contraction on the exact-fp32
                  matrix-core instruction (precision 0)
-  step_ms      - p10 / p50 / p90 of the per-round durations inside the timed
-                 region (timing events on a collector stream, no host sync)
+  structured_input - the same pipeline on the low-pass, translating stream
   dropin       - the six names of slam/core/features_utils.py driven as
                  slam/monocular/main_revamped.py drives them (one frame at a
                  time, host objects in and out): frames/s of that literal path
@@ -607,6 +617,10 @@ def _self_launch(args):
         cmd.append("--no-cpu-baseline")
     if args.no_extras:
         cmd.append("--no-extras")
+    if args.full:
+        cmd.append("--full")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", str(Path(args.dump_outputs).resolve())]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     res = subprocess.run(cmd, env=env, capture_output=True, text=True)
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -645,14 +659,62 @@ def calibrated_confidence_heads(sd, feats, ctx):
     return sd
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(pipe, out_dir):
+    """What the last round of `pipe` computed on this rank - the records its extractors wrote and the batched matches -
+    as out_dir/<name>.npy, padded to fixed shapes: per frame s of the round, `keypoints` [K, 2], `descriptors` [K, 128] and
+    `keypoint_scores` [K] (zeros past `keypoint_counts`[s]); per pair (s-1, s), `match_indices` [K, 2] (-1 past the count),
+    `match_scores` [K] (zeros past it) and `match_info` {matches, layers executed, n0, n1}.  Integers are stored as float64
+    (exact).  Frames 0..n-1 of the round only, n the most whose arrays fit in DUMP_BUDGET_BYTES (all 24 of the default
+    round).  Returns the names written."""
+    B, K = pipe.plan.frames_per_rank, pipe.K
+    ROW = importlib.import_module("opencv-simpleslam_amd.frame_shard").ROW      # x, y, descriptor floats per keypoint
+    info = pipe.infos()                                  # (synchronises; raises on a voided frame or pair)
+    per_frame = K * 2 * 4 + K * 128 * 4 + K * 4 + 8 + K * 2 * 8 + K * 4 + 4 * 8
+    n = max(1, min(B, DUMP_BUDGET_BYTES // per_frame))
+    s0 = pipe.last_set * B
+    slab = np.empty((B, pipe.REC), np.float32)
+    pipe.ctx.d2h(slab, pipe.rec_ptr(s0))
+    score = np.empty((B, K), np.float32)
+    pipe.ctx.d2h(score, pipe.score + s0 * K * 4)
+    ij = np.empty((B, K, 2), np.int32)
+    pipe.ctx.d2h(ij, pipe.ij)
+    msc = np.empty((B, K), np.float32)
+    pipe.ctx.d2h(msc, pipe.msc)
+    counts = np.ascontiguousarray(slab[:, K * ROW:K * ROW + 1]).view(np.int32)[:, 0]
+    valid = np.arange(K)[None, :] < counts[:, None]                       # [B, K]
+    matched = np.arange(K)[None, :] < np.maximum(info[:, :1], 0)
+    arrays = {
+        "keypoints": np.where(valid[..., None], slab[:, :2 * K].reshape(B, K, 2), 0).astype(np.float32),
+        "descriptors": np.where(valid[..., None], slab[:, 2 * K:K * ROW].reshape(B, K, 128), 0).astype(np.float32),
+        "keypoint_scores": np.where(valid, score, 0).astype(np.float32),
+        "keypoint_counts": counts.astype(np.float64),
+        "match_indices": np.where(matched[..., None], ij, -1).astype(np.float64),
+        "match_scores": np.where(matched, msc, 0).astype(np.float32),
+        "match_info": info.astype(np.float64),
+    }
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a[:n]))
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=140)         # x 24 frames: a timed region of ~3 s
     ap.add_argument("--warmup", type=int, default=8)          # a multiple of the 4-round input pool x 2 record sets: every graph key is captured
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the exact-f32 / BA / reproject legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the exact-f32 / BA / reproject ... legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the other inputs / precisions / sizes, the drop-in and CPU legs (runs of their own)")
     args = ap.parse_args()
+    args.full = args.full or os.environ.get("SSLAM_BENCH_FULL") == "1"      # --full for every call of a script (final_evidence.sh)
 
     rank = int(os.environ.get("RANK", 0))
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
@@ -663,7 +725,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
 
     cv2_classes_leg = None
-    if rank == 0 and world == 1 and not args.no_extras and os.environ.get("SSLAM_BENCH_FORCE_DIST") != "1":
+    if args.full and rank == 0 and world == 1 and not args.no_extras and os.environ.get("SSLAM_BENCH_FORCE_DIST") != "1":
         try:                                     # (child processes: before this one touches the GPU)
             cv2_classes_leg = dropin_cv2_classes_leg()
         except Exception as e:                   # never lose the headline line to an auxiliary leg
@@ -805,50 +867,57 @@ def main():
     if pipe.range_overflow():
         raise SystemExit("bench.py: a LightGlue activation left the fp16 range of the split-precision path inside the "
                          "timed region - the matches are not fp32-grade, the number is void")
-    # the dominant kernel inside the running pipeline: a few more rounds with every attention launch
-    # bracketed by HIP events on its matcher stream (event records are host-side, so these rounds run
-    # un-graphed; the bracket includes time the launch waits for CUs held by other streams' kernels)
-    for mat in mats:
-        mat.profile(True)
-    timed_rounds(pool, min(8, max(2, args.steps // 4)), 0)
-    attn_ms, attn_n = 0.0, 0
-    for mat in mats:
-        mat.profile(False)
-        ms_, n_ = mat.profile_read()
-        attn_ms += ms_; attn_n += n_
-    info = pipe.infos()
-    # Kernel-level figure for the roofline: one full batch replayed on ONE stream with the other
-    # streams idle.  In the timed region several streams share the chip, so the HIP-event bracket
-    # of a launch there also contains the time its blocks wait for CUs held by other streams'
-    # kernels; the single-stream bracket is the kernel's own duration (it is what rocprofv3
-    # --kernel-trace reports for the kernel in either mode).  Both are printed.
+    info = pipe.infos()                                      # the last timed round's {matches, layers, n0, n1}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(pipe, args.dump_outputs)
+
+    # everything below measures something other than `value`: --full only
+    attn_ms = attn_n = iso_ms = iso_n = lg_batch_ms = s_dt = s_info = None
     P = min(BATCH_PAIRS, FRAMES_PER_RANK - 1)
     K = MAX_KPTS
-    sb = pipe.last_set * FRAMES_PER_RANK                 # record set of the last round
-    pairs = [(pipe.xy_ptr(sb + s - 1), pipe.desc_ptr(sb + s - 1), K, pipe.xy_ptr(sb + s), pipe.desc_ptr(sb + s), K,
-              pipe.count_ptr(sb + s - 1), pipe.count_ptr(sb + s)) for s in range(1, P + 1)]
-    m0 = mats[0]
-    m0.profile(True)
-    for rep in range(3):
-        m0.match_batch_dev(pairs, pipe.ij + K * 8, pipe.msc + K * 4, pipe.info + 16, K, min_conf=MIN_CONF)
-    m0.ctx.sync()
-    m0.profile(False)
-    iso_ms, iso_n = m0.profile_read()
-    t0 = time.perf_counter()
-    for rep in range(3):
-        m0.match_batch_dev(pairs, pipe.ij + K * 8, pipe.msc + K * 4, pipe.info + 16, K, min_conf=MIN_CONF)
-    m0.ctx.sync()
-    lg_batch_ms = (time.perf_counter() - t0) / 3 * 1e3
+    if args.full:
+        # the dominant kernel inside the running pipeline: a few more rounds with every attention launch
+        # bracketed by HIP events on its matcher stream (event records are host-side, so these rounds run
+        # un-graphed; the bracket includes time the launch waits for CUs held by other streams' kernels)
+        for mat in mats:
+            mat.profile(True)
+        timed_rounds(pool, min(8, max(2, args.steps // 4)), 0)
+        attn_ms, attn_n = 0.0, 0
+        for mat in mats:
+            mat.profile(False)
+            ms_, n_ = mat.profile_read()
+            attn_ms += ms_; attn_n += n_
+        info = pipe.infos()
+        # Kernel-level figure for the roofline: one full batch replayed on ONE stream with the other
+        # streams idle.  In the timed region several streams share the chip, so the HIP-event bracket
+        # of a launch there also contains the time its blocks wait for CUs held by other streams'
+        # kernels; the single-stream bracket is the kernel's own duration (it is what rocprofv3
+        # --kernel-trace reports for the kernel in either mode).  Both are printed.
+        sb = pipe.last_set * FRAMES_PER_RANK                 # record set of the last round
+        pairs = [(pipe.xy_ptr(sb + s - 1), pipe.desc_ptr(sb + s - 1), K, pipe.xy_ptr(sb + s), pipe.desc_ptr(sb + s), K,
+                  pipe.count_ptr(sb + s - 1), pipe.count_ptr(sb + s)) for s in range(1, P + 1)]
+        m0 = mats[0]
+        m0.profile(True)
+        for rep in range(3):
+            m0.match_batch_dev(pairs, pipe.ij + K * 8, pipe.msc + K * 4, pipe.info + 16, K, min_conf=MIN_CONF)
+        m0.ctx.sync()
+        m0.profile(False)
+        iso_ms, iso_n = m0.profile_read()
+        t0 = time.perf_counter()
+        for rep in range(3):
+            m0.match_batch_dev(pairs, pipe.ij + K * 8, pipe.msc + K * 4, pipe.info + 16, K, min_conf=MIN_CONF)
+        m0.ctx.sync()
+        lg_batch_ms = (time.perf_counter() - t0) / 3 * 1e3
 
-    # second input of SURVEY 8(d): the structured (low-pass, translating) stream, same pipeline
-    spool = [c0.upload(np.stack([structured_frame(f) for f in plan.frames(r)])) for r in range(2)]
-    s_steps = max(2, args.steps // 4)
-    s_dt = timed_rounds(spool, s_steps, 2)
-    s_info = pipe.infos()
+        # second input of SURVEY 8(d): the structured (low-pass, translating) stream, same pipeline
+        spool = [c0.upload(np.stack([structured_frame(f) for f in plan.frames(r)])) for r in range(2)]
+        s_steps = max(2, args.steps // 4)
+        s_dt = timed_rounds(spool, s_steps, 2)
+        s_info = pipe.infos()
 
     # the auxiliary legs run at N = 1 only (they build pipelines of their own; at N > 1 every GPU-second of the lease
     # belongs to the scaling number)
-    extras = not args.no_extras and not distributed
+    extras = args.full and not args.no_extras and not distributed
     plane_frames = plan.frames_per_round()
 
     # early stop + point pruning under load: same pipeline, matchers whose token-confidence / matchability heads are
@@ -1055,7 +1124,7 @@ def main():
             except Exception as e:                       # never lose the headline line to an auxiliary leg
                 sized[name] = {"error": repr(e)}
 
-    times = np.array([dt, s_dt, x_dt or 0.0, e_dt or 0.0])
+    times = np.array([dt, s_dt or 0.0, x_dt or 0.0, e_dt or 0.0])
     if distributed:
         t = torch.tensor(times, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1065,10 +1134,6 @@ def main():
     if rank == 0:
         frames_total = args.steps * plan.frames_per_round()
         n0, n1, stop = int(info[-1, 2]), int(info[-1, 3]), int(info[-1, 1])
-        per_launch = attention_flops(n0, n1) * P
-        ach = per_launch / (iso_ms / max(iso_n, 1) * 1e-3) / 1e12 if iso_n else None
-        ach_region = attention_flops(n0, n1) * BATCH_PAIRS / (attn_ms / max(attn_n, 1) * 1e-3) / 1e12 if attn_n else None
-        traffic, traffic_src = _pmc_traffic()
         out = {
             "metric": "frames/sec ALIKED+LightGlue @1241x376",
             "value": round(frames_total / dt_max, 2),
@@ -1108,34 +1173,40 @@ def main():
                        "rccl_ranks": (comm.count() if distributed and backend == "rccl" else None),
                        "collation_backend": (("rccl (direct)" if backend == "rccl" else
                                               "gloo (host round trip" + (f"; RCCL not available: {rccl_fallback})" if rccl_fallback else ", test mode)")) if distributed else None)},
+        }
+        if args.full:
+            per_launch = attention_flops(n0, n1) * P
+            ach = per_launch / (iso_ms / max(iso_n, 1) * 1e-3) / 1e12 if iso_n else None
+            ach_region = attention_flops(n0, n1) * BATCH_PAIRS / (attn_ms / max(attn_n, 1) * 1e-3) / 1e12 if attn_n else None
+            traffic, traffic_src = _pmc_traffic()
             # achieved = ALGORITHMIC flops (8 n0 n1 256 per pair, x pairs per launch) / HIP-event launch
             # duration on an otherwise idle GPU; the kernel issues 20 v_mfma_f32_32x32x16_f16 per 32-key sub-step for 8
             # algorithmic products' worth (3 per product in K.Q^T, 2 in P.V): executed = 2.5x
-            "roofline": {"bound": "mfma", "kernel": "lg_attention_asm_p1_kernel (hand-scheduled gfx950 assembly; v_mfma_f32_32x32x16_f16: 3 per product in K.Q^T, 2 in P.V)",
-                         "achieved": round(ach, 2) if ach else None, "peak": F16_MFMA_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(ach / F16_MFMA_PEAK_TFLOPS, 4) if ach else None,
-                         # HBM-side bytes per launch from the committed PMC passes (FETCH_SIZE x2 + WRITE_SIZE,
-                         # scripts/pmc_traffic.sh); not re-measured here: PMC collection needs rocprofv3
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "executed_mfma_frac": round(2.5 * ach / F16_MFMA_PEAK_TFLOPS, 4) if ach else None,
-                         "pairs_per_launch": P, "launches_timed": iso_n,
-                         "avg_launch_us": round(iso_ms / max(iso_n, 1) * 1e3, 2),
-                         # the same launches inside the running pipeline (other streams' kernels share the chip)
-                         "in_pipeline_launches": attn_n,
-                         "in_pipeline_avg_bracket_us": round(attn_ms / max(attn_n, 1) * 1e3, 2),
-                         "in_pipeline_frac": round(ach_region / F16_MFMA_PEAK_TFLOPS, 4) if ach_region else None,
-                         "lightglue_batch_ms_isolated": round(lg_batch_ms, 3),
-                         "pipeline_algorithmic_tflops": round(
-                             frames_total / dt_max * (lightglue_gflop(min(n0, n1), stop) + ALIKED_GFLOP_PER_FRAME)
-                             / 1e3 / world, 2)},
-        }
-        out["structured_input"] = {
-            "value": round(s_steps * plan.frames_per_round() / s_dt_max, 2), "unit": "frames/s", "steps": s_steps,
-            "what": "same pipeline on the 9x9-box low-pass noise translating 3 px/frame (SURVEY 8(d))",
-            "matches_last_pair": int(s_info[-1, 0]), "lightglue_layers_executed": int(s_info[-1, 1]),
-            "lightglue_layers_histogram": {str(int(k)): int(v) for k, v in
-                                           zip(*np.unique(s_info[s_info[:, 2] > 0, 1], return_counts=True))},
-            "kpts_matched": [int(s_info[-1, 2]), int(s_info[-1, 3])]}
+            out["roofline"] = {"bound": "mfma", "kernel": "lg_attention_asm_p1_kernel (hand-scheduled gfx950 assembly; v_mfma_f32_32x32x16_f16: 3 per product in K.Q^T, 2 in P.V)",
+                               "achieved": round(ach, 2) if ach else None, "peak": F16_MFMA_PEAK_TFLOPS,
+                               "unit": "TFLOP/s", "frac": round(ach / F16_MFMA_PEAK_TFLOPS, 4) if ach else None,
+                               # HBM-side bytes per launch from the committed PMC passes (FETCH_SIZE x2 + WRITE_SIZE,
+                               # scripts/pmc_traffic.sh); not re-measured here: PMC collection needs rocprofv3
+                               "traffic": traffic, "traffic_source": traffic_src,
+                               "executed_mfma_frac": round(2.5 * ach / F16_MFMA_PEAK_TFLOPS, 4) if ach else None,
+                               "pairs_per_launch": P, "launches_timed": iso_n,
+                               "avg_launch_us": round(iso_ms / max(iso_n, 1) * 1e3, 2),
+                               # the same launches inside the running pipeline (other streams' kernels share the chip)
+                               "in_pipeline_launches": attn_n,
+                               "in_pipeline_avg_bracket_us": round(attn_ms / max(attn_n, 1) * 1e3, 2),
+                               "in_pipeline_frac": round(ach_region / F16_MFMA_PEAK_TFLOPS, 4) if ach_region else None,
+                               "lightglue_batch_ms_isolated": round(lg_batch_ms, 3),
+                               "pipeline_algorithmic_tflops": round(
+                                   frames_total / dt_max * (lightglue_gflop(min(n0, n1), stop) + ALIKED_GFLOP_PER_FRAME)
+                                   / 1e3 / world, 2)}
+        if s_dt is not None:
+            out["structured_input"] = {
+                "value": round(s_steps * plan.frames_per_round() / s_dt_max, 2), "unit": "frames/s", "steps": s_steps,
+                "what": "same pipeline on the 9x9-box low-pass noise translating 3 px/frame (SURVEY 8(d))",
+                "matches_last_pair": int(s_info[-1, 0]), "lightglue_layers_executed": int(s_info[-1, 1]),
+                "lightglue_layers_histogram": {str(int(k)): int(v) for k, v in
+                                               zip(*np.unique(s_info[s_info[:, 2] > 0, 1], return_counts=True))},
+                "kpts_matched": [int(s_info[-1, 2]), int(s_info[-1, 3])]}
         if e_info is not None:
             e_steps = max(4, args.steps // 4)
             ok = e_info[:, 2] > 0
@@ -1176,7 +1247,7 @@ def main():
                 v, c = out["dropin"]["value"], cv2_classes_leg.get("value")
                 if c:
                     cv2_classes_leg["vs_duck_types"] = round(c / v, 3)      # (against the in-process leg above; `vs_duck_types_same_conditions`: against its partner child)
-        if not args.no_cpu_baseline and world == 1:        # the CPU leg is reported at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:        # the CPU leg is reported at N = 1 only
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
 

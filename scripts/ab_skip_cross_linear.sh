@@ -7,7 +7,7 @@ cd $GRAFT_REPO_ROOT
 for rep in 1 2; do
   for fl in "" "-DSSLAM_DBG_SKIP_CROSS_LINEAR=1"; do
     SSLAM_EXTRA_HIPCC_FLAGS="$fl" python opencv-simpleslam_amd/build.py > /tmp/ab_build.log 2>&1 || { tail -5 /tmp/ab_build.log; continue; }
-    v=$(python bench.py --no-extras --no-cpu-baseline --steps 100 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['lightglue_batch_ms_isolated'])")
+    v=$(python bench.py --full --no-extras --no-cpu-baseline --steps 100 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['lightglue_batch_ms_isolated'])")
     echo "flags [$fl]: frames/s, ms per round, isolated 8-pair forward ms: $v"
   done
 done

@@ -12,6 +12,7 @@ mkdir -p gpurun_out
 DIGEST=$(python opencv-simpleslam_amd/build.py --digest)
 echo "== $TAG: csrc digest $DIGEST, head $HEAD"
 timeout -k 10 1100 python -m pytest tests -m gpu -q > gpurun_out/${TAG}_gputest.log 2>&1; tail -2 gpurun_out/${TAG}_gputest.log
+export SSLAM_BENCH_FULL=1         # from here on every bench.py call is a --full one: the evidence line carries all the legs
 timeout -k 10 900 python bench.py > gpurun_out/${TAG}_bench_n1.json 2> gpurun_out/${TAG}_bench_n1.err; tail -2 gpurun_out/${TAG}_bench_n1.err
 bash scripts/prof_bench.sh $TAG 40 > gpurun_out/${TAG}_bench_concurrency.txt 2>&1
 bash scripts/prof_lg_batch.sh 8 > gpurun_out/${TAG}_lightglue_batch8_kernels.txt 2>&1; cp gpurun_out/lgb_kernel_stats.csv gpurun_out/${TAG}_lightglue_batch8_kernel_stats.csv

@@ -11,6 +11,7 @@ pytestmark = pytest.mark.gpu
 def _run_bench(extra_env, cmd):
     import json, os, subprocess, sys
     env = dict(os.environ, SSLAM_BENCH_FRAMES="6", SSLAM_BENCH_NE="1", SSLAM_BENCH_NM="2", SSLAM_BENCH_PAIRS="4", **extra_env)
+    env.pop("SSLAM_BENCH_FULL", None)                        # plain or --full: the command line says which
     out = subprocess.run(cmd, cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -20,7 +21,7 @@ def _run_bench(extra_env, cmd):
 
 def test_bench_contract_single_rank():
     import sys
-    d = _run_bench({}, [sys.executable, "bench.py", "--steps", "2", "--warmup", "4", "--no-cpu-baseline"])
+    d = _run_bench({}, [sys.executable, "bench.py", "--steps", "2", "--warmup", "4", "--no-cpu-baseline", "--full"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                 "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "structured_input",
                 "exact_f32", "ba", "reproject", "step_ms", "timed_region_s", "early_stop", "dropin", "pcie", "c5", "kpts4000", "f16x3", "build",
@@ -60,6 +61,36 @@ def test_bench_contract_single_rank():
     cv = d["dropin"]["cv2_classes"]
     assert cv.get("value", 0) > 0 and cv["matches_median"] > 100 and cv["slam_loop"]["value"] > 0, cv
     assert cv["duck_types_same_conditions"]["value"] > 0 and cv["answered_from"]["ahead"] > 0, cv
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) prints the headline line with no leg that needs runs of its own, and --dump-outputs writes
+    what the last timed round computed: fixed-shape float32 / float64 arrays, the round's records and matches."""
+    import sys
+    import numpy as np
+    d = _run_bench({}, [sys.executable, "bench.py", "--steps", "3", "--warmup", "4", "--dump-outputs", str(tmp_path / "out")])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup",
+                "step_ms", "timed_region_s", "config", "build"):
+        assert key in d
+    assert d["steps"] == 3 and d["value"] > 0 and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert abs(d["ms_per_step"] * 3 / 1e3 - d["timed_region_s"]) <= 1e-3              # ms_per_step: one of the 3 timed steps
+    for leg in ("roofline", "structured_input", "exact_f32", "early_stop", "planted_matches", "pcie", "f16x3", "c5",
+                "kpts4000", "ba", "reproject", "dropin", "cpu_baseline"):
+        assert leg not in d, leg
+    B, K = 6, 2048                                       # SSLAM_BENCH_FRAMES of _run_bench, MAX_KPTS
+    shapes = {"keypoints": (B, K, 2), "descriptors": (B, K, 128), "keypoint_scores": (B, K), "keypoint_counts": (B,),
+              "match_indices": (B, K, 2), "match_scores": (B, K), "match_info": (B, 4)}
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == sorted(f"{n}.npy" for n in shapes)
+    a = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in shapes}
+    for n, shp in shapes.items():
+        assert a[n].shape == shp and a[n].dtype in (np.float32, np.float64), (n, a[n].shape, a[n].dtype)
+        assert np.isfinite(a[n]).all(), n
+    cnt = a["keypoint_counts"].astype(int)
+    assert (cnt > 0).all() and (cnt <= K).all() and (a["match_info"][:, 2] >= 0).all()
+    for s in range(B):                                   # real keypoints up to the count, padding behind it
+        assert np.abs(a["descriptors"][s, :cnt[s]]).sum(1).min() > 0 and not a["descriptors"][s, cnt[s]:].any()
+        m = int(a["match_info"][s, 0])
+        assert (a["match_indices"][s, m:] == -1).all() and (a["match_indices"][s, :m] >= 0).all()
 
 
 def test_bench_self_launches_its_ranks():
