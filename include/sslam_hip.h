@@ -150,6 +150,42 @@ int sslam_fmat_ransac_dev(sslam_ctx* ctx, int n_max, const int32_t* n_dev, const
                           int max_iters, unsigned char* mask_out_dev, int32_t* ij_out_dev,
                           double* F_out_dev, int32_t* info_out_dev);
 
+/* --------------------------------------------------------------- PnP-RANSAC
+ * Replaces `cv2.solvePnPRansac(pts3d, pts2d, K, None, flags=cv2.SOLVEPNP_ITERATIVE, ...)` inside
+ * `solve_pnp_ransac` (slam/core/pnp_utils.py:307-341) and `refine_pose_pnp` (:200-221): OpenCV 4.x's
+ * classic path (EPnP on 5-point samples of the cv::RNG stream, float32 reprojection error, final
+ * Levenberg-Marquardt on the winner's inliers), scored on the GPU.  Parity with cv2 itself is unpinned
+ * (tests/pnp_oracle.py names what could not be confirmed).
+ *   pts3d_f32[n*3], pts2d_f32[n*2] (host), n >= 5 (4: OpenCV's P3P branch, not covered; fewer: the caller
+ *   returns early);  K9 row-major 3x3 (fx, fy, cx, cy are read; skew ignored as projectPoints does)
+ *   Tcw_init16 (may be NULL): only whether it is given matters - with a guess OpenCV starts the final
+ *   refinement from the LAST sample's EPnP pose (its RANSAC callback writes every sample into the guess
+ *   buffers), without one from the winner's; n == 5: one EPnP on all points, all inliers, no refinement
+ *   reproj_px: inlier iff float ||ip - proj||^2 <= (float)(px^2), px rounded to float first
+ *   confidence in (0,1); max_iters 0..100000 (0 acts as 1)
+ *   mask_out[n]: the RANSAC winner's inliers (1);  Tcw_out16: row-major 4x4 camera-from-world
+ *   info_out[4] (may be NULL): inliers (-1: no model, cv2 returns False), samples the sequential loop
+ *   ran, winning sample, LM iterations */
+int sslam_pnp_ransac_host(sslam_ctx* ctx, int n, const float* pts3d_f32, const float* pts2d_f32,
+                          const double* K9, const double* Tcw_init16, double reproj_px, double confidence,
+                          int max_iters, unsigned char* mask_out, double* Tcw_out16, int* info_out);
+
+/* Device-resident form (enqueue only, no host round trip): consumes what `sslam_reproject_match_dev`
+ * wrote - kp_of_point_dev[n_points], the map's pts3d_dev[n_points*3] doubles and the keypoints
+ * kp_xy_dev[*][2] - and compacts the correspondences in map order (the order of the overlay's
+ * Matches2D3D), cast to float32 as the reference does.  K9 / Tcw_init16 stay host values (as above).
+ *   mask_out_dev[n_points] (may be NULL): inlier flags of the compacted correspondences
+ *   Tcw_out_dev[16] double: the pose (identity when there is none);  n_out_dev (may be NULL): the
+ *   correspondence count;  info_out_dev[4] int32 as info_out above; fewer than 5 correspondences
+ *   (4 included) give info[0] = -1
+ * The context's scratch buffer is (re)allocated when n_points or max_iters grows: call once with the
+ * largest before capturing or pipelining. */
+int sslam_pnp_ransac_dev(sslam_ctx* ctx, int n_points, const int32_t* kp_of_point_dev,
+                         const double* pts3d_dev, const float* kp_xy_dev, const double* K9,
+                         const double* Tcw_init16, double reproj_px, double confidence, int max_iters,
+                         unsigned char* mask_out_dev, double* Tcw_out_dev, int32_t* n_out_dev,
+                         int32_t* info_out_dev);
+
 /* ------------------------------------------- 2D-3D association for tracking
  * Replaces the per-point loop of `reproject_and_match_2d3d` (slam/core/pnp_utils.py:224-304) for
  * float descriptors: projection (`_project_points` :127-141), radius search (cKDTree :238, :265),

@@ -1,21 +1,24 @@
-"""Drop-in for the descriptor-matching half of the reference's `slam/core/pnp_utils.py`:
-`reproject_and_match_2d3d` (pnp_utils.py:224-304) on the HIP backend, plus the cv2-free helpers
-around it (`Matches2D3D`, `_project_points`, `predict_pose_const_vel`).  The PnP solvers of that
-module (`solve_pnp_ransac`, `refine_pose_pnp`) call cv2 and stay with the reference; a maintainer
-patches in just this function:
+"""Drop-in for the reference's `slam/core/pnp_utils.py` on the HIP backend: `reproject_and_match_2d3d`
+(pnp_utils.py:224-304), the PnP solvers `solve_pnp_ransac` (:307-341) and `refine_pose_pnp` (:200-221) - OpenCV's
+classic `solvePnPRansac(SOLVEPNP_ITERATIVE)` restated on the GPU, no cv2 - plus the cv2-free helpers around them
+(`Matches2D3D`, `_project_points`, `predict_pose_const_vel`).  A maintainer patches in the functions:
 
     import slam.core.pnp_utils as ref
-    ref.reproject_and_match_2d3d = amd_pnp_utils.reproject_and_match_2d3d
+    for name in ("reproject_and_match_2d3d", "solve_pnp_ransac", "refine_pose_pnp"):
+        setattr(ref, name, getattr(amd_pnp_utils, name))
+
+Four correspondences (OpenCV's P3P minimal solver) are outside this backend's scope and raise NotImplementedError.
 """
 from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import List
+from typing import List, Optional, Tuple
 
 import numpy as np
 
 from ... import _native
+from ... import pnp as _pnp
 
 DESC_DIM = 128
 MAX_OBS_CHECK = 6
@@ -149,3 +152,40 @@ def _dev_scratch(ctx, Q, N):
         cur["_ptrs"] = (cur["kp"], cur["des"], cur["out"], cur["info"])
         ctx.scratch["reproject"] = cur
     return cur
+
+
+def _pnp_inputs(pts3d, pts2d):
+    p3 = np.asarray(pts3d, np.float32).reshape(-1, 3)
+    p2 = np.asarray(pts2d, np.float32).reshape(-1, 2)
+    if len(p3) == 4:
+        raise NotImplementedError("4 correspondences: OpenCV takes its P3P minimal solver there, which this backend "
+                                  "does not cover (the tracker asks for >= --pnp_min_inliers, default 30)")
+    return p3, p2
+
+
+def solve_pnp_ransac(pts3d: np.ndarray, pts2d: np.ndarray, K: np.ndarray, ransac_px: float,
+                     Tcw_init: Optional[np.ndarray] = None, iters: int = 200,
+                     conf: float = 0.999, ctx=None) -> Tuple[Optional[np.ndarray], np.ndarray]:
+    """Same signature and result as the reference: (T_cw, inlier_mask) or (None, empty).  Only whether `Tcw_init` is
+    given matters: OpenCV then starts its final refinement from the last RANSAC sample's pose (see pnp.py)."""
+    if len(pts3d) < 4:
+        return None, np.zeros((0,), dtype=bool)
+    p3, p2 = _pnp_inputs(pts3d, pts2d)
+    ok, T, mask, _ = _pnp.solve_pnp_ransac(p3, p2, K, float(ransac_px), float(conf), int(iters),
+                                           use_guess=Tcw_init is not None, ctx=ctx)
+    if not ok or int(mask.sum()) < 4:
+        return None, np.zeros((len(p3),), dtype=bool)
+    return T, mask
+
+
+def refine_pose_pnp(K: np.ndarray, pts3d: np.ndarray, pts2d: np.ndarray, ransac_px: float = 2.0, ctx=None):
+    """Same signature and result as the reference: (R, t) float64, or (None, None)."""
+    p3 = np.asarray(pts3d, dtype=np.float32)
+    p2 = np.asarray(pts2d, dtype=np.float32)
+    if len(p3) < 4 or len(p2) < 4:
+        return None, None
+    p3, p2 = _pnp_inputs(p3, p2)
+    ok, T, _, _ = _pnp.solve_pnp_ransac(p3, p2, K, float(ransac_px), 0.999, 200, use_guess=False, ctx=ctx)
+    if not ok:
+        return None, None
+    return T[:3, :3].astype(np.float64), T[:3, 3].astype(np.float64)
