@@ -147,20 +147,13 @@ int sslam_ba_residual_jacobian_host(sslam_ctx* ctx, int n_obs, const int32_t* po
     }
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t N = (size_t)n_obs;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = sslam::align_up(off + bytes, 256); return o; };
+    sslam::Carver carve;
     const size_t o_pi = carve(N * 4), o_xi = carve(N * 4), o_uv = carve(N * 16);
     const size_t o_q = carve((size_t)n_poses * 32), o_t = carve((size_t)n_poses * 24);
     const size_t o_X = carve((size_t)n_points * 24), o_in = carve(32);
     const size_t o_r = carve(N * 16), o_Jq = carve(N * 64), o_Jt = carve(N * 48), o_JX = carve(N * 48);
-    if (off > ctx->ba_scratch_bytes) {
-        if (ctx->ba_scratch) SSLAM_HIP_CHECK(hipFree(ctx->ba_scratch));
-        ctx->ba_scratch = nullptr;
-        ctx->ba_scratch_bytes = 0;
-        SSLAM_HIP_CHECK(hipMalloc(&ctx->ba_scratch, off));
-        ctx->ba_scratch_bytes = off;
-    }
-    char* b = (char*)ctx->ba_scratch;
+    char* b;
+    if (int rc = sslam::ctx_scratch(ctx, carve.bytes, &b)) return rc;
     hipStream_t s = ctx->stream;
     SSLAM_HIP_CHECK(hipMemcpyAsync(b + o_pi, pose_idx, N * 4, hipMemcpyHostToDevice, s));
     SSLAM_HIP_CHECK(hipMemcpyAsync(b + o_xi, point_idx, N * 4, hipMemcpyHostToDevice, s));

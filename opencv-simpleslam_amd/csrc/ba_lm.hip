@@ -20,6 +20,7 @@
 // the reduced system (<= 72 x 72) is factored by one workgroup in LDS.
 #include "common.hpp"
 #include "ba_math.hpp"
+#include "geom_common.hpp"
 
 namespace {
 
@@ -63,29 +64,8 @@ struct LMArgs {
     LMCtrl* ctrl;
 };
 
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ double block_max(double v, double* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + s]);
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
+using sslam::block_max;
+using sslam::block_sum;
 
 __device__ __forceinline__ void load_obs(const LMArgs& a, int i, int buf, sslam::BAObsIn& in) {
     const int pi = a.obs_pose[i], xi = a.obs_point[i];
@@ -617,8 +597,7 @@ extern "C" int sslam_ba_solve_host(sslam_ctx* ctx, int n_obs, const int32_t* pos
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t N = (size_t)n_obs, P = (size_t)n_poses, Q = (size_t)n_points, m = 6 * (size_t)Po;
     const int nb_obs = sslam::cdiv(n_obs, LM_T), nb_pt = sslam::cdiv(n_points, LM_T);
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = sslam::align_up(off + bytes + 8, 256); return o; };
+    sslam::Carver carve;
     const size_t o_pi = carve(N * 4), o_xi = carve(N * 4), o_sl = carve(N * 4), o_uv = carve(N * 16);
     const size_t o_pp = carve((Q + 1) * 4), o_po = carve(N * 4), o_sp = carve((Po + 1) * 4), o_so = carve(ps_obs.size() * 4);
     const size_t o_slp = carve((size_t)Po * 4), o_psl = carve(P * 4), o_in = carve(32);
@@ -634,14 +613,8 @@ extern "C" int sslam_ba_solve_host(sslam_ctx* ctx, int n_obs, const int32_t* pos
     const size_t o_pc = carve((size_t)nb_obs * 8), o_pm = carve((size_t)nb_obs * 8), o_pb = carve((size_t)nb_obs * 4);
     const size_t o_ps = carve((size_t)nb_pt * 8), o_px = carve((size_t)nb_pt * 8), o_pg = carve((size_t)nb_pt * 8);
     const size_t o_ctrl = carve(sizeof(LMCtrl));
-    if (off > ctx->ba_scratch_bytes) {
-        if (ctx->ba_scratch) SSLAM_HIP_CHECK(hipFree(ctx->ba_scratch));
-        ctx->ba_scratch = nullptr;
-        ctx->ba_scratch_bytes = 0;
-        SSLAM_HIP_CHECK(hipMalloc(&ctx->ba_scratch, off));
-        ctx->ba_scratch_bytes = off;
-    }
-    char* b = (char*)ctx->ba_scratch;
+    char* b;
+    if (int rc = sslam::ctx_scratch(ctx, carve.bytes, &b)) return rc;
     hipStream_t s = ctx->stream;
     auto up = [&](size_t o, const void* src, size_t bytes) {
         return bytes ? hipMemcpyAsync(b + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;

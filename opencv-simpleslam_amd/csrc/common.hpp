@@ -35,6 +35,13 @@ void set_error(const char* fmt, ...);
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Carves one scratch slab into pieces: carve(n) places the next n bytes on a 256-byte boundary, at least 8 guard bytes
+// past the piece before, and returns their offset; `bytes` is the slab size so far.
+struct Carver {
+    size_t bytes = 0;
+    size_t operator()(size_t n) { const size_t o = bytes; bytes = align_up(bytes + n + 8, 256); return o; }
+};
+
 // Bump allocator over one hipMalloc'd slab: every instance sizes its workspace
 // once at create time, so the launch path never calls hipMalloc (graph-safe).
 struct Arena {
@@ -184,9 +191,9 @@ struct sslam_ctx {
     hipStream_t stream = nullptr;
     bool owns_stream = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // scratch for the *_host BA entry point (grown on demand, outside any graph)
-    void* ba_scratch = nullptr;
-    size_t ba_scratch_bytes = 0;
+    // scratch slab of the geometry entries (BA, LM, RANSAC, PnP, 2D-3D association); sslam::ctx_scratch owns it
+    void* scratch = nullptr;
+    size_t scratch_bytes = 0;
     // instances (ALIKED / LightGlue) created on this context; sslam_ctx_destroy with instances alive only marks
     // the context closed and the last instance's destroy frees it (a garbage collector may finalise a context
     // before its instances; their destroy still needs the stream)
@@ -196,4 +203,7 @@ struct sslam_ctx {
 namespace sslam {
 void ctx_retain(sslam_ctx* ctx);
 void ctx_release(sslam_ctx* ctx);      // frees a closed context when its last instance goes
+// *base = the context's scratch slab, grown to `bytes` first when it is smaller.  Growing drains the context's stream
+// (work enqueued earlier may still use the old slab) and reallocates: a pipeline sizes it once, with its largest problem.
+int ctx_scratch(sslam_ctx* ctx, size_t bytes, char** base);
 }

@@ -66,6 +66,20 @@ void ctx_retain(sslam_ctx* ctx) { ++ctx->instances; }
 void ctx_release(sslam_ctx* ctx) {
     if (--ctx->instances == 0 && ctx->closed) ctx_free(ctx);
 }
+int ctx_scratch(sslam_ctx* ctx, size_t bytes, char** base) {
+    if (bytes > ctx->scratch_bytes) {
+        if (ctx->scratch) {
+            SSLAM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            SSLAM_HIP_CHECK(hipFree(ctx->scratch));
+        }
+        ctx->scratch = nullptr;
+        ctx->scratch_bytes = 0;
+        SSLAM_HIP_CHECK(hipMalloc(&ctx->scratch, bytes));
+        ctx->scratch_bytes = bytes;
+    }
+    *base = (char*)ctx->scratch;
+    return 0;
+}
 }  // namespace sslam
 }
 
@@ -83,7 +97,7 @@ int sslam_ctx_destroy(sslam_ctx* ctx) {
 static void ctx_free(sslam_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->ba_scratch) (void)hipFree(ctx->ba_scratch);
+    if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);

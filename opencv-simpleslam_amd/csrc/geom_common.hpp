@@ -1,0 +1,94 @@
+// geom_common.hpp - device helpers shared by the geometry kernels (ransac_kernels.hip, pnp_kernels.hip, ba_lm.hip).
+//
+// The RANSAC pieces restate OpenCV 4.x's classic ptsetreg.cpp; both RANSAC files must stay bit-exact with the numpy
+// restatements under oracle/, so they share one copy.  Nothing here holds a contractible multiply-add: pnp_kernels.hip
+// compiles with `fp contract(off)` and the other files do not, and both must see the same arithmetic.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+
+namespace sslam {
+
+// cv::RNG: multiply-with-carry on a 64-bit state
+struct CvRng {
+    unsigned long long state;
+    __device__ __forceinline__ unsigned next() {
+        state = (unsigned long long)(unsigned)state * 4164903690ULL + (unsigned)(state >> 32);
+        return (unsigned)state;
+    }
+    __device__ __forceinline__ int uniform(int a, int b) { return a == b ? a : (int)(next() % (unsigned)(b - a) + a); }
+};
+
+// RANSACUpdateNumIters(p, ep, modelPoints, maxIters)
+__device__ __forceinline__ int update_num_iters(double p, double ep, int model_points, int max_iters) {
+    p = fmax(p, 0.0); p = fmin(p, 1.0);
+    ep = fmax(ep, 0.0); ep = fmin(ep, 1.0);
+    double num = fmax(1.0 - p, DBL_MIN);
+    double denom = 1.0 - pow(1.0 - ep, (double)model_points);
+    if (denom < DBL_MIN) return 0;
+    num = log(num);
+    denom = log(denom);
+    return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)rint(num / denom);
+}
+
+// getSubset's draw: MP distinct indices in [0, n), a duplicate is drawn again
+template <int MP>
+__device__ __forceinline__ void draw_distinct(CvRng& rng, int n, int* idx) {
+#pragma unroll
+    for (int i = 0; i < MP; ++i) {
+        int v;
+        bool dup;
+        do {
+            v = rng.uniform(0, n);
+            dup = false;
+#pragma unroll
+            for (int j = 0; j < i; ++j) dup |= idx[j] == v;
+        } while (dup);
+        idx[i] = v;
+    }
+}
+
+// Fixed-order tree reduction in LDS over a power-of-two workgroup: NT threads when the launch fixes it, else blockDim.x.
+// Every thread calls it and gets the result; `sh` holds one element per thread.
+// `op(acc, v)` folds v into acc in place.
+template <int NT = 0, typename T, typename Op>
+__device__ __forceinline__ T block_reduce(T v, T* sh, Op op) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = (NT ? NT : (int)blockDim.x) >> 1; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) op(sh[threadIdx.x], sh[threadIdx.x + s]);
+        __syncthreads();
+    }
+    const T r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+template <int NT = 0, typename T>
+__device__ __forceinline__ T block_sum(T v, T* sh) { return block_reduce<NT>(v, sh, [](T& acc, T x) { acc += x; }); }
+
+template <int NT = 0>
+__device__ __forceinline__ double block_max(double v, double* sh) {
+    return block_reduce<NT>(v, sh, [](double& acc, double x) { acc = fmax(acc, x); });
+}
+
+// One turn of an order-preserving compaction over a workgroup of NT threads (a multiple of 64; every thread calls it):
+// a thread whose `keep` is set gets emit(o), o = the number of items kept before its own - in earlier turns, then by
+// lower threads of this one.  `wsum` (NT / 64 ints) and `base` (the running count, 0 before the first turn) are LDS.
+template <int NT, typename Emit>
+__device__ __forceinline__ void block_compact(bool keep, int* wsum, int& base, Emit emit) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) wsum[w] = __popcll(bal);
+    __syncthreads();
+    int o = base;
+    for (int j = 0; j < w; ++j) o += wsum[j];
+    o += __popcll(bal & ((1ull << lane) - 1));
+    if (keep) emit(o);
+    __syncthreads();
+    if (threadIdx.x == NT - 1) base = o + keep;           // the last thread's rank + its own item: the new running count
+    __syncthreads();
+}
+
+}  // namespace sslam

@@ -5,7 +5,7 @@
 // `refine_pose_pnp` (pnp_utils.py:200-221).
 //
 // The algorithm is OpenCV 4.x's classic (non-USAC) path, restated from its published source (solvepnp.cpp, epnp.cpp,
-// calibration.cpp, compat_ptsetreg.cpp, ptsetreg.cpp); tests/pnp_oracle.py is the restatement in numpy, with every
+// calibration.cpp, compat_ptsetreg.cpp, ptsetreg.cpp); oracle/pnp_ref.py is the restatement in numpy, with every
 // point that could not be confirmed named there:
 //   * float32 correspondences; model_points 5, minimal solver EPnP on undistortPoints' float32 normalized points;
 //     n == 5: one EPnP on all points, all inliers, no refinement;
@@ -24,14 +24,17 @@
 // replays the sample stream chunk by chunk, a workgroup per sample solves EPnP (fp64, LDS) and scores the model against
 // every correspondence, one lane replays the best / budget logic.  Eight launches per call, whatever the data: head
 // [compaction of the association's output (device entry), control block, samples of chunk 0] - per chunk [solve +
-// score] and [replay + samples of the next chunk] - tail [replay, the winner's mask, the LM start] - LM.
+// score] and [replay + samples of the next chunk] - tail [replay, the winner's mask, the LM start] - LM.  cv::RNG,
+// RANSACUpdateNumIters, getSubset's draw and the workgroup reduction / compaction come from geom_common.hpp, shared with
+// ransac_kernels.hip.
 #include "common.hpp"
 
 #include <algorithm>
 #include <cfloat>
 
-// bit-for-bit agreement with the restatement: no fused multiply-adds in this file
+// bit-for-bit agreement with the restatement: no fused multiply-adds in this file (the shared helpers included)
 #pragma clang fp contract(off)
+#include "geom_common.hpp"
 
 namespace {
 
@@ -79,48 +82,15 @@ struct PNArgs {
     PNCtrl* ctrl;
 };
 
-// ---- cv::RNG ----------------------------------------------------------------------------------------------------------
-struct CvRng {
-    unsigned long long state;
-    __device__ unsigned next() {
-        state = (unsigned long long)(unsigned)state * 4164903690ULL + (unsigned)(state >> 32);
-        return (unsigned)state;
-    }
-    __device__ int uniform(int a, int b) { return a == b ? a : (int)(next() % (unsigned)(b - a) + a); }
-};
-
-// RANSACUpdateNumIters(p, ep, modelPoints, maxIters)
-__device__ int update_num_iters(double p, double ep, int model_points, int max_iters) {
-    p = fmax(p, 0.0); p = fmin(p, 1.0);
-    ep = fmax(ep, 0.0); ep = fmin(ep, 1.0);
-    double num = fmax(1.0 - p, DBL_MIN);
-    double denom = 1.0 - pow(1.0 - ep, (double)model_points);
-    if (denom < DBL_MIN) return 0;
-    num = log(num);
-    denom = log(denom);
-    return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)rint(num / denom);
-}
-
 // samples [h0, h1) of the stream (one lane; the draws depend on n only)
 __device__ void pn_draw(const PNArgs& a, int h0, int h1) {
     PNCtrl* c = a.ctrl;
     if (c->mode != 0 || h0 != c->niters || h0 >= c->budget) return;
     const int n = c->n, end = min(h1, c->budget);
-    CvRng rng{c->rng_state};
+    sslam::CvRng rng{c->rng_state};
     for (int it = h0; it < end; ++it) {
         int idx[PN_MP];
-#pragma unroll
-        for (int i = 0; i < PN_MP; ++i) {
-            int v;
-            bool dup;
-            do {
-                v = rng.uniform(0, n);
-                dup = false;
-#pragma unroll
-                for (int j = 0; j < i; ++j) dup |= idx[j] == v;
-            } while (dup);
-            idx[i] = v;
-        }
+        sslam::draw_distinct<PN_MP>(rng, n, idx);
 #pragma unroll
         for (int i = 0; i < PN_MP; ++i) a.subsets[it * PN_MP + i] = idx[i];
     }
@@ -139,7 +109,7 @@ __device__ void pn_select(const PNArgs& a, int h0, int h1) {
         if (good > max(c->max_good, PN_MP - 1)) {
             c->max_good = good;
             c->best_h = it;
-            c->budget = update_num_iters(a.confidence, (double)(n - good) / n, PN_MP, c->budget);
+            c->budget = sslam::update_num_iters(a.confidence, (double)(n - good) / n, PN_MP, c->budget);
         }
     }
     c->niters = it;
@@ -600,18 +570,6 @@ __device__ __forceinline__ float pn_error(const double* R, const double* t, cons
     return __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
 }
 
-__device__ __forceinline__ int block_sum_int(int v, int* sh) {          // any power-of-two block, fixed order
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const int tot = sh[0];
-    __syncthreads();
-    return tot;
-}
-
 // ---- solve sample h, score its model against every correspondence (workgroup / sample) ---------------------------------
 __global__ __launch_bounds__(PN_T) void pn_models_score_kernel(PNArgs a) {
     __shared__ EpnpLds e;
@@ -637,7 +595,7 @@ __global__ __launch_bounds__(PN_T) void pn_models_score_kernel(PNArgs a) {
     int good = 0;
     for (int i = threadIdx.x; i < n; i += PN_T)
         good += pn_error(R, t, a, a.p3[3 * i], a.p3[3 * i + 1], a.p3[3 * i + 2], a.p2[2 * i], a.p2[2 * i + 1]) <= a.thresh2;
-    good = block_sum_int(good, sh);
+    good = sslam::block_sum(good, sh);
     if (threadIdx.x == 0) a.counts[h] = good;
 }
 
@@ -645,7 +603,6 @@ __global__ __launch_bounds__(PN_T) void pn_models_score_kernel(PNArgs a) {
 __global__ __launch_bounds__(PN_HEAD_T) void pn_head_kernel(PNArgs a) {
     __shared__ int wsum[PN_HEAD_T / 64], base;
     PNCtrl* c = a.ctrl;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int n = a.n_max;
     if (a.kp_of_point) {
         // order-preserving compaction of the association (the order of Matches2D3D), cast to float32 as the reference does
@@ -654,23 +611,13 @@ __global__ __launch_bounds__(PN_HEAD_T) void pn_head_kernel(PNArgs a) {
         for (int q0 = 0; q0 < a.n_max; q0 += PN_HEAD_T) {
             const int q = q0 + threadIdx.x;
             const int kp = q < a.n_max ? a.kp_of_point[q] : -1;
-            const bool keep = kp >= 0;
-            const unsigned long long bal = __ballot(keep);
-            if (lane == 0) wsum[w] = __popcll(bal);
-            __syncthreads();
-            int off = base;
-            for (int j = 0; j < w; ++j) off += wsum[j];
-            if (keep) {
-                const int o = off + __popcll(bal & ((1ull << lane) - 1));
+            sslam::block_compact<PN_HEAD_T>(kp >= 0, wsum, base, [&](int o) {
                 a.p3[3 * o] = (float)a.map_xyz[3 * (size_t)q];
                 a.p3[3 * o + 1] = (float)a.map_xyz[3 * (size_t)q + 1];
                 a.p3[3 * o + 2] = (float)a.map_xyz[3 * (size_t)q + 2];
                 a.p2[2 * o] = a.kp_xy[2 * (size_t)kp];
                 a.p2[2 * o + 1] = a.kp_xy[2 * (size_t)kp + 1];
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) { int s = 0; for (int j = 0; j < PN_HEAD_T / 64; ++j) s += wsum[j]; base += s; }
-            __syncthreads();
+            });
         }
         n = base;
     }
@@ -939,24 +886,12 @@ void pn_enqueue(hipStream_t s, PNArgs a) {
 struct PNScratch { size_t p3, p2, sub, mod, cnt, mask, start, T, info, n, ctrl, total; };
 PNScratch pn_layout(size_t N, size_t H) {
     PNScratch L{};
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = sslam::align_up(off + bytes + 8, 256); return o; };
+    sslam::Carver carve;
     L.p3 = carve(N * 12); L.p2 = carve(N * 8); L.sub = carve(H * PN_MP * 4); L.mod = carve(H * 48);
     L.cnt = carve(H * 4); L.mask = carve(N); L.start = carve(48); L.T = carve(128); L.info = carve(16); L.n = carve(4);
     L.ctrl = carve(sizeof(PNCtrl));
-    L.total = off;
+    L.total = carve.bytes;
     return L;
-}
-
-int pn_reserve(sslam_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->ba_scratch_bytes) return 0;
-    // (re)allocation synchronises the device: a pipeline sizes the scratch once, with its largest problem
-    if (ctx->ba_scratch) SSLAM_HIP_CHECK(hipFree(ctx->ba_scratch));
-    ctx->ba_scratch = nullptr;
-    ctx->ba_scratch_bytes = 0;
-    SSLAM_HIP_CHECK(hipMalloc(&ctx->ba_scratch, bytes));
-    ctx->ba_scratch_bytes = bytes;
-    return 0;
 }
 
 int pn_args(sslam_ctx* ctx, int n_max, const double* K9, int use_guess, double reproj_px, double confidence,
@@ -967,8 +902,7 @@ int pn_args(sslam_ctx* ctx, int n_max, const double* K9, int use_guess, double r
     max_iters = std::max(max_iters, 1);
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     L = pn_layout((size_t)std::max(n_max, 1), (size_t)max_iters);
-    if (int rc = pn_reserve(ctx, L.total)) return rc;
-    b = (char*)ctx->ba_scratch;
+    if (int rc = sslam::ctx_scratch(ctx, L.total, &b)) return rc;
     a = PNArgs{};
     a.n_max = n_max; a.max_iters = max_iters; a.use_guess = use_guess;
     a.fx = K9[0]; a.fy = K9[4]; a.cx = K9[2]; a.cy = K9[5];

@@ -23,8 +23,10 @@
 // wide (workgroup per sample); (b) is then replayed exactly by one lane over the stored scores.
 // The result is what the sequential loop would have produced.  Seven launches per call (r05):
 // head [gather, control block, samples of chunk 0] - per chunk [solve + score] and [replay +
-// samples of the next chunk] - tail [replay, winner, mask, compaction].
+// samples of the next chunk] - tail [replay, winner, mask, compaction].  cv::RNG, RANSACUpdateNumIters, getSubset's draw
+// and the workgroup reduction / compaction come from geom_common.hpp, shared with pnp_kernels.hip.
 #include "common.hpp"
+#include "geom_common.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -72,16 +74,6 @@ struct RSArgs {
 
 __device__ __forceinline__ int rs_n(const RSArgs& a) { return a.n_dev ? min(max(a.n_dev[0], 0), a.n) : a.n; }
 
-// ---- cv::RNG ------------------------------------------------------------------------------
-struct CvRng {
-    unsigned long long state;
-    __device__ unsigned next() {
-        state = (unsigned long long)(unsigned)state * 4164903690ULL + (unsigned)(state >> 32);
-        return (unsigned)state;
-    }
-    __device__ int uniform(int a, int b) { return a == b ? a : (int)(next() % (unsigned)(b - a) + a); }
-};
-
 // haveCollinearPoints(m, count): last point against every earlier pair
 __device__ bool last_point_collinear(const float* p, const int* idx, int count) {
     const int i = count - 1;
@@ -95,18 +87,6 @@ __device__ bool last_point_collinear(const float* p, const int* idx, int count) 
         }
     }
     return false;
-}
-
-// RANSACUpdateNumIters(p, ep, modelPoints, maxIters)
-__device__ int update_num_iters(double p, double ep, int model_points, int max_iters) {
-    p = fmax(p, 0.0); p = fmin(p, 1.0);
-    ep = fmax(ep, 0.0); ep = fmin(ep, 1.0);
-    double num = fmax(1.0 - p, DBL_MIN);
-    double denom = 1.0 - pow(1.0 - ep, (double)model_points);
-    if (denom < DBL_MIN) return 0;
-    num = log(num);
-    denom = log(denom);
-    return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)rint(num / denom);
 }
 
 // ---- 1. replay the sample stream for samples [h0, h1) (one lane) ------------------------------
@@ -138,7 +118,7 @@ __device__ void rs_subsets_step(const RSArgs& a, int h0, int h1, float* rs_pts, 
     const int q = lane % 15, set = lane / 15;
     int tj = 1, tk = 0;
     for (int t = 0; t < q; ++t) { if (++tk == tj) { ++tj; tk = 0; } }        // q -> (j, k): (1,0) (2,0) (2,1) (3,0) ...
-    CvRng rng{c->rng_state};
+    sslam::CvRng rng{c->rng_state};
     const int end = min(h1, c->budget);
     int made = c->n_subsets;
     bool exhausted = false;
@@ -146,18 +126,7 @@ __device__ void rs_subsets_step(const RSArgs& a, int h0, int h1, float* rs_pts, 
         int idx[RS_MP];
         int attempts = 0;
         for (; attempts < RS_SUBSET_ATTEMPTS; ++attempts) {
-            if (lane == 0) {
-                for (int i = 0; i < RS_MP; ++i) {
-                    int v;
-                    bool dup;
-                    do {
-                        v = rng.uniform(0, n);
-                        dup = false;
-                        for (int j = 0; j < i; ++j) dup |= idx[j] == v;
-                    } while (dup);
-                    idx[i] = v;
-                }
-            }
+            if (lane == 0) sslam::draw_distinct<RS_MP>(rng, n, idx);
 #pragma unroll
             for (int i = 0; i < RS_MP; ++i) idx[i] = __shfl(idx[i], 0);
             bool bad = false;
@@ -332,18 +301,6 @@ __device__ __forceinline__ float fm_error(const double* F, float x1, float y1, f
 // ---- 2 + 3. solve sample h and score its models against every match (workgroup / sample) -----------------------
 // r05: one launch instead of two (thread / sample, then workgroup / model): the solver is a serial fp64 chain of ~10 us
 // whatever the grid, and the 1 - 3 models of a sample are scored by the workgroup that has them in LDS.
-__device__ __forceinline__ int rs_block_sum(int v, int* sh) {      // sum over the workgroup (RS_T threads), valid in every thread
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = RS_T / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const int tot = sh[0];
-    __syncthreads();
-    return tot;
-}
-
 __global__ __launch_bounds__(RS_T) void rs_models_score_kernel(RSArgs a) {
     __shared__ double As[RS_MP * 9];
     __shared__ double Fm[27];
@@ -383,7 +340,7 @@ __global__ __launch_bounds__(RS_T) void rs_models_score_kernel(RSArgs a) {
         int good = 0;
         for (int i = threadIdx.x; i < n; i += RS_T)
             good += fm_error(F, a.p1[2 * i], a.p1[2 * i + 1], a.p2[2 * i], a.p2[2 * i + 1]) <= t;
-        good = rs_block_sum(good, sh);
+        good = sslam::block_sum<RS_T>(good, sh);
         if (threadIdx.x == 0) a.counts[h * 3 + k] = good;
     }
 }
@@ -407,7 +364,7 @@ __device__ void rs_select_step(const RSArgs& a, int h0, int h1) {
                 if (good > max(c->max_good, RS_MP - 1)) {
                     c->max_good = good;
                     c->best_h = it; c->best_k = k;
-                    c->budget = update_num_iters(a.confidence, (double)(n - good) / n, RS_MP, c->budget);
+                    c->budget = sslam::update_num_iters(a.confidence, (double)(n - good) / n, RS_MP, c->budget);
                 }
             }
     }
@@ -432,7 +389,7 @@ __global__ __launch_bounds__(RS_T) void rs_head_kernel(RSArgs a, float* p1w, flo
     if (threadIdx.x == 0) {
         c->lmeds = n <= RS_LMEDS_MAX;
         c->budget = max(a.max_iters, 1);
-        if (c->lmeds) c->budget = max(update_num_iters(a.confidence, 0.45, RS_MP, a.max_iters), 1);   // LMeDS: fixed budget
+        if (c->lmeds) c->budget = max(sslam::update_num_iters(a.confidence, 0.45, RS_MP, a.max_iters), 1);   // LMeDS: fixed budget
         c->rng_state = 0xffffffffffffffffULL;
         c->n_subsets = 0; c->exhausted = 0;
         c->best_h = c->best_k = -1;
@@ -509,19 +466,9 @@ __global__ __launch_bounds__(1024) void rs_tail_kernel(RSArgs a) {
     for (int i0 = 0; i0 < n; i0 += 1024) {
         const int i = i0 + threadIdx.x;
         const bool keep = i < n && !none && a.mask[i];          // (this thread's own store above)
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) wsum[w] = __popcll(bal);
-        __syncthreads();
-        int off = base;
-        for (int j = 0; j < w; ++j) off += wsum[j];
-        if (keep && a.ij_out) {
-            const int o = off + __popcll(bal & ((1ull << lane) - 1));
-            a.ij_out[2 * o] = a.ij[2 * i];
-            a.ij_out[2 * o + 1] = a.ij[2 * i + 1];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) { int tsum = 0; for (int j = 0; j < 16; ++j) tsum += wsum[j]; base += tsum; }
-        __syncthreads();
+        sslam::block_compact<1024>(keep, wsum, base, [&](int o) {
+            if (a.ij_out) { a.ij_out[2 * o] = a.ij[2 * i]; a.ij_out[2 * o + 1] = a.ij[2 * i + 1]; }
+        });
     }
     if (threadIdx.x == 0) {
         if (a.info_out) {
@@ -565,23 +512,11 @@ void rs_enqueue(hipStream_t s, RSArgs a, int max_iters, float* p1w, float* p2w) 
 struct RSScratch { size_t p1, p2, sub, mod, nm, cnt, med, mask, ctrl, total; };
 RSScratch rs_layout(size_t N, size_t H) {
     RSScratch L{};
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = sslam::align_up(off + bytes + 8, 256); return o; };
+    sslam::Carver carve;
     L.p1 = carve(N * 8); L.p2 = carve(N * 8); L.sub = carve(H * RS_MP * 4); L.mod = carve(H * 27 * 8);
     L.nm = carve(H * 4); L.cnt = carve(H * 12); L.med = carve(H * 12); L.mask = carve(N); L.ctrl = carve(sizeof(RSCtrl));
-    L.total = off;
+    L.total = carve.bytes;
     return L;
-}
-
-int rs_reserve(sslam_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->ba_scratch_bytes) return 0;
-    // (re)allocation synchronises the device: a pipeline sizes the scratch once, with its largest problem
-    if (ctx->ba_scratch) SSLAM_HIP_CHECK(hipFree(ctx->ba_scratch));
-    ctx->ba_scratch = nullptr;
-    ctx->ba_scratch_bytes = 0;
-    SSLAM_HIP_CHECK(hipMalloc(&ctx->ba_scratch, bytes));
-    ctx->ba_scratch_bytes = bytes;
-    return 0;
 }
 
 }  // namespace
@@ -598,8 +533,8 @@ extern "C" int sslam_fmat_ransac_dev(sslam_ctx* ctx, int n_max, const int32_t* n
     if (max_iters <= 0 || max_iters > RS_MAX_ITERS) max_iters = RS_MAX_ITERS;
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     const RSScratch L = rs_layout((size_t)n_max, (size_t)max_iters);
-    if (int rc = rs_reserve(ctx, L.total)) return rc;
-    char* b = (char*)ctx->ba_scratch;
+    char* b;
+    if (int rc = sslam::ctx_scratch(ctx, L.total, &b)) return rc;
     hipStream_t s = ctx->stream;
     RSArgs a{};
     a.n = n_max; a.n_dev = n_dev; a.max_iters = max_iters; a.thresh = thresh; a.confidence = confidence;
@@ -627,8 +562,8 @@ extern "C" int sslam_fmat_ransac_host(sslam_ctx* ctx, int n, const float* pts1, 
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t N = (size_t)n;
     const RSScratch L = rs_layout(N, (size_t)max_iters);
-    if (int rc = rs_reserve(ctx, L.total)) return rc;
-    char* b = (char*)ctx->ba_scratch;
+    char* b;
+    if (int rc = sslam::ctx_scratch(ctx, L.total, &b)) return rc;
     const size_t o_p1 = L.p1, o_p2 = L.p2, o_mask = L.mask, o_ctrl = L.ctrl;
     hipStream_t s = ctx->stream;
     SSLAM_HIP_CHECK(hipMemcpyAsync(b + o_p1, pts1, N * 8, hipMemcpyHostToDevice, s));

@@ -133,24 +133,14 @@ namespace {
 struct RPScratch { char* base; size_t K, T, uv, cn, ck, cd, out, info, pts, cnt, od, kp, des; };
 
 int rp_scratch(sslam_ctx* ctx, size_t Q, size_t N, bool host_inputs, RPScratch& sc) {
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = sslam::align_up(off + bytes + 8, 256); return o; };
+    sslam::Carver carve;
     sc.K = carve(72); sc.T = carve(128); sc.uv = carve(Q * 8); sc.cn = carve(Q * 4);
     sc.ck = carve(Q * RP_MAXC * 4); sc.cd = carve(Q * RP_MAXC * 4); sc.out = carve(Q * 4); sc.info = carve(16);
     if (host_inputs) {
         sc.pts = carve(Q * 24); sc.cnt = carve(Q * 4); sc.od = carve(Q * 6 * RP_DIM * 4);
         sc.kp = carve(N * 8); sc.des = carve(N * RP_DIM * 4);
     }
-    if (off > ctx->ba_scratch_bytes) {
-        (void)hipStreamSynchronize(ctx->stream);          // earlier enqueued work may still use the old slab
-        if (ctx->ba_scratch) SSLAM_HIP_CHECK(hipFree(ctx->ba_scratch));
-        ctx->ba_scratch = nullptr;
-        ctx->ba_scratch_bytes = 0;
-        SSLAM_HIP_CHECK(hipMalloc(&ctx->ba_scratch, off));
-        ctx->ba_scratch_bytes = off;
-    }
-    sc.base = (char*)ctx->ba_scratch;
-    return 0;
+    return sslam::ctx_scratch(ctx, carve.bytes, &sc.base);
 }
 
 // enqueue the two kernels on device-resident inputs; K9 / Tcw16 are host values

@@ -26,6 +26,9 @@ Parity status (see DESIGN.md section "Oracle pinning"):
                              property the reference's own BA test pins.
   * `oracle.ransac_ref`    - PARITY UNPINNED (opencv_python==4.11.0.86 absent):
                              OpenCV's classic findFundamentalMat path restated.
+  * `oracle.pnp_ref`       - PARITY UNPINNED (opencv_python==4.11.0.86 absent):
+                             OpenCV's classic solvePnPRansac(SOLVEPNP_ITERATIVE) path
+                             restated; its docstring names what could not be confirmed.
   * `oracle.reproject_ref` - PINNED against the reference's own
                              `slam/core/pnp_utils.py::reproject_and_match_2d3d` run
                              under a cv2 stub (tests/golden/reproject_match.npz).

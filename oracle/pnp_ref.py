@@ -1,6 +1,6 @@
 """CPU restatement: `cv2.solvePnPRansac(pts3d, pts2d, K, None, flags=cv2.SOLVEPNP_ITERATIVE, ...)`.
 
-TEST INFRASTRUCTURE ONLY, like oracle/: numpy, sequential, the yardstick of csrc/pnp_kernels.hip.  It follows the
+TEST INFRASTRUCTURE ONLY (see oracle/__init__.py): numpy, sequential, the yardstick of csrc/pnp_kernels.hip.  It follows the
 reference's two call sites, slam/core/pnp_utils.py `solve_pnp_ransac` (:307-341, with and without `Tcw_init`) and
 `refine_pose_pnp` (:200-221, no guess, 200 iterations).
 

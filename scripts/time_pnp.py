@@ -2,7 +2,7 @@
   host entry   sslam_pnp_ransac_host: upload + 8 launches + download (the drop-in's solve_pnp_ransac)
   device chain sslam_reproject_match_dev (SoA map) + sslam_pnp_ransac_dev on its output, nothing read back
   PnP alone    sslam_pnp_ransac_dev on a device-resident association
-and the numpy restatement (tests/pnp_oracle.py) beside them for scale.  usage: python scripts/time_pnp.py [REPS]"""
+and the numpy restatement (oracle/pnp_ref.py) beside them for scale.  usage: python scripts/time_pnp.py [REPS]"""
 import ctypes as C
 import importlib
 import sys
@@ -13,8 +13,8 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
-import pnp_oracle as O
 import pnp_scenes as S
+from oracle import pnp_ref as O
 
 N = importlib.import_module("opencv-simpleslam_amd._native")
 PN = importlib.import_module("opencv-simpleslam_amd.pnp")

@@ -1,10 +1,10 @@
-"""The numpy restatement of OpenCV's solvePnPRansac(SOLVEPNP_ITERATIVE) (tests/pnp_oracle.py) against ground truth:
+"""The numpy restatement of OpenCV's solvePnPRansac(SOLVEPNP_ITERATIVE) (oracle/pnp_ref.py) against ground truth:
 the yardstick of the GPU tests has to be right first."""
 import numpy as np
 import pytest
 
-import pnp_oracle as O
 import pnp_scenes as S
+from oracle import pnp_ref as O
 
 
 def _pose(r, t):

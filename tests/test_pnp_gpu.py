@@ -1,13 +1,13 @@
 """PnP-RANSAC on the MI355X (csrc/pnp_kernels.hip) against the numpy restatement of OpenCV's classic
-solvePnPRansac(SOLVEPNP_ITERATIVE) (tests/pnp_oracle.py), plus the host / device entries, the association -> PnP chain
+solvePnPRansac(SOLVEPNP_ITERATIVE) (oracle/pnp_ref.py), plus the host / device entries, the association -> PnP chain
 on the device and the edge cases."""
 import numpy as np
 import pytest
 
-import pnp_oracle as O
 import pnp_scenes as S
 import reproject_scenes as RS
 from conftest import load_pkg
+from oracle import pnp_ref as O
 
 pytestmark = pytest.mark.gpu
 
