@@ -2,6 +2,7 @@
 import numpy as np
 
 K = np.array([[718.856, 0, 607.1928], [0, 718.856, 185.2157], [0, 0, 1.0]])
+T_VIEW = np.array([0.3, -0.05, 1.1])          # translation of the second view
 
 
 def make_matches(n, outlier_frac=0.3, noise=0.3, seed=0, planar=False):
@@ -11,7 +12,7 @@ def make_matches(n, outlier_frac=0.3, noise=0.3, seed=0, planar=False):
         X[:, 2] = 20.0 + 0.1 * X[:, 0]
     ang = 0.05
     R = np.array([[np.cos(ang), 0, np.sin(ang)], [0, 1, 0], [-np.sin(ang), 0, np.cos(ang)]])
-    t = np.array([0.3, -0.05, 1.1])
+    t = T_VIEW
     x1 = (K @ X.T).T
     x2 = (K @ (R @ X.T + t[:, None])).T
     p1 = x1[:, :2] / x1[:, 2:]
