@@ -34,6 +34,7 @@
 #include "gemm_f16x3.hpp"
 #include "gemm_f16x3_big.hpp"
 #include "ffn_fused.hpp"
+#include "lg_plan.hpp"
 
 namespace {
 
@@ -54,12 +55,13 @@ using sslam::panel_index;
 using sslam::mfma16;
 using sslam::split_f32;
 using sslam::SPLIT_INV;
+using sslam::LGHooks; using sslam::LGPlan; using sslam::LGAttn; using sslam::LGMerge; using sslam::LGLinears; using sslam::LGFfnTile;   // lg_plan.hpp
 
 constexpr int D = 256;       // descriptor_dim
 constexpr int DH = 64;       // head dim
-constexpr int NH = 4;        // heads
+constexpr int NH = sslam::LG_NH;    // heads (lg_plan.hpp)
 constexpr int DIN = 128;     // ALIKED descriptor dim
-constexpr int NL = 9;        // layers
+constexpr int NL = sslam::LG_NL;    // layers
 constexpr int ENC = 32;      // rotary frequencies per token
 
 struct LGCtrl {
@@ -319,8 +321,8 @@ __global__ __launch_bounds__(256) void lg_ln_gelu_kernel(float* __restrict__ hid
 //     S^T = K.Q^T so a lane owns one query column: softmax runs over registers
 //     (+ one cross-half exchange) and P feeds PV straight from the accumulator.
 // ------------------------------------------------------------------------ //
-constexpr int AQ = 128;          // queries per block
-constexpr int AK = 64;           // keys per LDS tile
+constexpr int AQ = sslam::LG_AQ;          // queries per block (lg_plan.hpp)
+constexpr int AK = sslam::LG_AK;           // keys per LDS tile
 constexpr int AK_LD = DH + 4;
 
 struct __attribute__((aligned(16))) AttnSmem {
@@ -1554,7 +1556,7 @@ struct AttnArgsH {
     float* o_part; float* m_part; float* l_part;      // key-split partials (KS > 1)
     SplitOut msg;                                     // KS == 1: the normalised context goes straight to the split planes
     int KS; int Kc; int NIc; const LGCtrl* ctrl;
-    int p_single;                                     // precision study only (sslam_lightglue_debug_split_form bit 0x04): P as ONE fp16 plane
+    int p_single;                                     // P as ONE fp16 plane: precision "f16x3p1" (the default) or sslam_lightglue_debug_split_form bit 0x04
 };
 
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
@@ -1940,18 +1942,10 @@ struct sslam_lightglue {
     int *ind, *gmap, *prune, *arg0, *arg1;
     float *in_xy, *in_desc, *up_xy, *up_desc, *out_score;
     int32_t *out_ij, *out_info;
-    // split-precision planes (precision == 1)
-    int precision = 1;               // 0: fp32 MFMA everywhere; 1: fp16 hi/lo split planes (three MFMAs per product; with p_single two in P.V)
-    bool sim_exact = false;          // SSLAM_LG_SIM_EXACT=1 (experiments): the similarity GEMM stays on the fp32 matrix instruction at precision 1
-    int dbg_layers = NL;             // test hook: run only the first dbg_layers layers
-    int dbg_self_only = 0;           // test hook: stop after the self block of the last executed layer
-    int force_ks = 0;                // test hook: key split of the attention launches (0 = by batch size)
+    LGHooks hooks;                   // precision and the test hooks, as their setters store them; lg_plan (lg_plan.hpp) reads them once per enqueue
     hipError_t launch_error = hipSuccess;   // first failure of a module-API launch (checked with hipGetLastError at the end of an enqueue)
-    int p_single = 1;                // precision "f16x3p1" (set_precision 2, the DEFAULT since r05 - profiles/r05_flip_soak.md): P as one fp16 plane in P.V, row sums over the rounded weights
-    int study = 0;                   // precision study (sslam_lightglue_debug_split_form): which cross terms of the split products are dropped
-    _Float16* zero_plane = nullptr;  // study only: an all-zero fp16 plane standing in for a dropped low plane
-    int big_gemm = -1;               // test hook: -1 by batch size, 0 / 1 force the single-pair (ring) / batched form of the linears;
-                                     // 2 / 3: batched form with 64- / 32-token FFN tiles whatever the size
+    _Float16* zero_plane = nullptr;  // precision study only (hooks.study): an all-zero fp16 plane standing in for a dropped low plane
+    // split-precision planes (LGPlan::split)
     _Float16 *w_hi, *w_lo;           // whole weight blob, split
     _Float16 *ffn_w1f[NL][2], *ffn_w2f[NL][2];   // fused-FFN fragment-order weights, [layer][self / cross]
     _Float16 *xs_hi, *xs_lo, *msgs_hi, *msgs_lo, *hids_hi, *hids_lo;
@@ -2017,22 +2011,6 @@ float conf_threshold(int layer) {   // np.clip(0.8 + 0.1 * exp(-4 i / n_layers),
     return (float)v;
 }
 
-// key split of one attention launch: enough (image, head, query-block) units to give every CU two
-// workgroups without it, otherwise split the keys (partials + merge launch)
-int attn_key_split(const sslam_lightglue* g, int NI) {
-    int ks = 1;
-    if (g->force_ks > 100) ks = g->force_ks - 100;     // (test hook: forced split, assembly kernel)
-    else if (g->force_ks > 0) ks = g->force_ks;        // (test hook: forced split, the 4-wave r02 kernel)
-    else if (g->force_ks < 0 && g->force_ks > -4) ks = 1;    // (test hooks, no key split: -1 the 4-wave r02 kernel, -3 the assembly kernel)
-    else {                                             // 0, -4 = the same policy on the 4-wave r02 kernel, -5 = on the assembly kernel with the merge as a launch
-        // one workgroup per CU is the measured optimum of the assembly kernel (2048-keypoint pair, 128 units: no split 1.68 ms
-        // per forward, 2 ranges 1.59, 4 ranges 1.65; the 4-wave kernel 1.69 at 2 or 4)
-        const int units = NI * NH * (g->Kc / AQ);
-        while (ks < 4 && units * ks < 256 && g->Kc / AK >= 2 * ks * 4) ks *= 2;
-    }
-    return ks > g->KSmax ? g->KSmax : ks;
-}
-
 template <int BM, int BN, int TM, int TN, int EPI>
 void launch_linear(hipStream_t s, const LinearArgs& a) {
     dim3 grid(a.N / BN, a.NI * sslam::cdiv(a.Kc, BM));
@@ -2056,9 +2034,9 @@ void attn_event(sslam_lightglue* g, hipStream_t s, bool start) {
     if (!start) g->ev_used += 2;
 }
 
-void launch_attention(sslam_lightglue* g, hipStream_t s, int NI, const float* Q, const float* K,
+void launch_attention(sslam_lightglue* g, hipStream_t s, const LGPlan& plan, int NI, const float* Q, const float* K,
                       const float* V, int cross) {
-    const int KS = attn_key_split(g, NI);
+    const int KS = plan.ks;
     AttnArgs a{Q, K, V, cross, g->o_part, g->m_part, g->l_part, KS, g->Kc, g->NIc, g->ctrl};
     dim3 grid(sslam::cdiv(g->Kc, AQ), NI * NH, KS);
     attn_event(g, s, true);
@@ -2157,18 +2135,18 @@ int lg_load_attention_asm(int device) {
     return 0;
 }
 
-void launch_attention_h(sslam_lightglue* g, hipStream_t s, int NI, SplitPtr Q, SplitPtr K, SplitPtr VT, int cross,
-                        bool merge_in_ffn = false) {
-    const int KS = attn_key_split(g, NI);
-    if (g->study) {       // precision study: a dropped cross term = its low-plane operand replaced by zeros (bit-identical to not issuing the MFMA)
-        if (g->study & 0x01) K.lo = g->zero_plane;          // S = kh.qh + kh.ql          (K as one fp16 plane)
-        if (g->study & 0x02) Q.lo = g->zero_plane;          // S = kh.qh + kl.qh          (Q as one fp16 plane)
-        if (g->study & 0x08) VT.lo = g->zero_plane;         // O = vh.ph + vh.pl          (V as one fp16 plane)
+void launch_attention_h(sslam_lightglue* g, hipStream_t s, const LGPlan& plan, int NI, SplitPtr Q, SplitPtr K, SplitPtr VT,
+                        int cross) {
+    const int KS = plan.ks, study = g->hooks.study;
+    if (study) {          // precision study: a dropped cross term = its low-plane operand replaced by zeros (bit-identical to not issuing the MFMA)
+        if (study & 0x01) K.lo = g->zero_plane;             // S = kh.qh + kh.ql          (K as one fp16 plane)
+        if (study & 0x02) Q.lo = g->zero_plane;             // S = kh.qh + kl.qh          (Q as one fp16 plane)
+        if (study & 0x08) VT.lo = g->zero_plane;            // O = vh.ph + vh.pl          (V as one fp16 plane)
     }
     AttnArgsH a{Q, K, VT, cross, g->o_part, g->m_part, g->l_part, SplitOut{g->msgs_hi, g->msgs_lo}, KS, g->Kc,
-                g->NIc, g->ctrl, ((g->study & 0x04) || g->p_single) ? 1 : 0};     // O = vh.ph + vl.ph: study bit 0x04 (4-wave kernel only) or precision "f16x3p1"
+                g->NIc, g->ctrl, plan.p_single ? 1 : 0};     // O = vh.ph + vl.ph: study bit 0x04 (4-wave kernel only) or precision "f16x3p1"
     attn_event(g, s, true);
-    if (!(g->study & 0x04) && (g->force_ks == 0 || g->force_ks == -3 || g->force_ks == -5 || g->force_ks > 100)) {
+    if (plan.attn == LGAttn::Asm) {
         // the hand-scheduled assembly kernel - the arithmetic, LDS images and results of lg_attention_p_kernel (no key split: batched
         // launches, debug_key_split(lg, -3)) and of lg_attention_p_kernel's key ranges (single pairs) bit for bit, 8 - 10 % faster
         // (profiles/r03_attention_experiments.md)
@@ -2178,7 +2156,7 @@ void launch_attention_h(sslam_lightglue* g, hipStream_t s, int NI, SplitPtr Q, S
         k.magic = k.nqb > 1 ? (unsigned)((1ull << 32) / (unsigned)k.nqb + 1) : 0u;
         size_t sz = sizeof(k);
         void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-        const hipFunction_t fn = g->p_single ? g_attn_asm_p1_fn[g->ctx->device] : g_attn_asm_fn[g->ctx->device];
+        const hipFunction_t fn = plan.p_single ? g_attn_asm_p1_fn[g->ctx->device] : g_attn_asm_fn[g->ctx->device];
         const hipError_t e = hipModuleLaunchKernel(fn, (unsigned)k.nqb, (unsigned)k.nslab, 1,
                                                    256, 1, 1, 0, s, nullptr, cfg);
         if (e != hipSuccess && g->launch_error == hipSuccess) g->launch_error = e;
@@ -2188,33 +2166,28 @@ void launch_attention_h(sslam_lightglue* g, hipStream_t s, int NI, SplitPtr Q, S
         hipLaunchKernelGGL(lg_attention_p_kernel, grid, dim3(256), 0, s, a);
     }
     attn_event(g, s, false);
-    if (KS == 1 || merge_in_ffn) return;   // the kernel wrote the context planes itself / the fused FFN merges the partials
+    if (plan.merge != LGMerge::Launch) return;   // the kernel wrote the context planes itself / the fused FFN merges the partials
     const long n4 = (long)NI * NH * g->Kc * 16;
     hipLaunchKernelGGL(lg_attn_merge_h_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, g->o_part,
                        g->m_part, g->l_part, SplitOut{g->msgs_hi, g->msgs_lo}, KS, g->Kc, NI, g->NIc, g->ctrl);
 }
 
 // one transformer layer (self + cross block) on the split-precision path
-// `heads`: the layer's cross-block FFN also evaluates the token heads on the new state (batched form only; returns whether
-// it did - otherwise lg_token_heads_kernel has to run)
-bool lg_layer_h(sslam_lightglue* g, hipStream_t s, int NI, const LGLayerW& l, int layer, bool self_only, bool heads) {
+// `heads`: the layer's cross-block FFN also evaluates the token heads on the new state (LGPlan::heads_in_ffn, not the last layer)
+void lg_layer_h(sslam_lightglue* g, hipStream_t s, const LGPlan& plan, int NI, const LGLayerW& l, int layer, bool self_only,
+                bool heads) {
     const SplitPtr xs{g->xs_hi, g->xs_lo}, msgs{g->msgs_hi, g->msgs_lo};
     const SplitPtr hids{g->hids_hi, g->hids_lo}, none{nullptr, nullptr};
     const SplitPtr qs{g->qs_hi, g->qs_lo}, ks{g->ks_hi, g->ks_lo}, vts{g->vts_hi, g->vts_lo};
     // precision study (sslam_lightglue_debug_split_form): W.x products with one cross term dropped - the READ side of the
     // activation (0x10 projections, 0x20 FFN) or weight (0x40 projections, 0x80 FFN) low plane is an all-zero plane
-    const int st = g->study;
+    const int st = g->hooks.study;
     auto act = [&](SplitPtr a, int bit) { if (st & bit) a.lo = g->zero_plane; return a; };
     auto wgt = [&](LinearArgsH& a, int bit) { if (st & bit) a.W.lo = g->zero_plane; };
     const unsigned tokblocks = sslam::cdiv(NI * g->Kc, 4);
     const float sm_scale = 0.125f * 1.4426950408889634f;        // 1/sqrt(64) * log2(e)
-    // enough token rows for 128-row tiles to fill the chip (a batch of pairs): 128 x 128 projections and the
-    // whole FFN as ONE kernel (ffn_fused.hpp); a single pair keeps the 64-row ring kernels (r01 form)
-    const bool big = g->big_gemm >= 0 ? g->big_gemm != 0 : ((long)NI * g->Kc >= 4096 && g->Kc % 128 == 0);
-    // one pair: the attention's key-range partials are merged by the FFN tiles (ffn_fused.hpp FOLD), not by a launch of their own
-    const int KS = attn_key_split(g, NI);
-    const bool small_tiles = g->big_gemm == 3 || (g->big_gemm != 2 && NI * (g->Kc / 64) <= 128);
-    const bool fold = big && small_tiles && KS > 1 && st == 0 && (g->force_ks == 0 || g->force_ks > 100);   // (test hooks -4 / -5: the merge launch)
+    // Big: 128 x 128 projections and the whole FFN as ONE kernel (ffn_fused.hpp); Ring: the 64-row ring kernels (r01 form)
+    const bool big = plan.linears == LGLinears::Big;
     auto ffn = [&](int cross, const float* w1, const float* b1, const float* lnw, const float* lnb, const float* w2,
                    const float* b2) {
         if (big) {
@@ -2230,11 +2203,11 @@ bool lg_layer_h(sslam_lightglue* g, hipStream_t s, int NI, const LGLayerW& l, in
                 k.f.conf_thr = conf_threshold(layer); k.f.conf = g->conf; k.f.mat = g->mat;
             }
             k.ctrl = g->ctrl; k.Kc = g->Kc;
-            if (fold) {                            // one pair, keys split into ranges: the tile merges the partials itself
+            if (plan.merge == LGMerge::InFfn) {    // one pair, keys split into ranges: the tile merges the partials itself
                 k.f.o_part = g->o_part; k.f.m_part = g->m_part; k.f.l_part = g->l_part;
-                k.f.ks = KS; k.f.part_zs = (long)g->NIc * NH * g->Kc;
+                k.f.ks = plan.ks; k.f.part_zs = (long)g->NIc * NH * g->Kc;
                 hipLaunchKernelGGL((lg_ffn_fused_kernel<1, true>), dim3(NI * (g->Kc / 32)), dim3(512), sslam::FFN_LDS_BYTES, s, k);
-            } else if (small_tiles)                // too few 64-token tiles for the chip: 32-token tiles (same results)
+            } else if (plan.ffn_tile == LGFfnTile::T32)    // too few 64-token tiles for the chip: 32-token tiles (same results)
                 hipLaunchKernelGGL(lg_ffn_fused_kernel<1>, dim3(NI * (g->Kc / 32)), dim3(512), sslam::FFN_LDS_BYTES, s, k);
             else
                 hipLaunchKernelGGL(lg_ffn_fused_kernel<2>, dim3(NI * (g->Kc / 64)), dim3(512), sslam::FFN_LDS_BYTES, s, k);
@@ -2259,9 +2232,9 @@ bool lg_layer_h(sslam_lightglue* g, hipStream_t s, int NI, const LGLayerW& l, in
         if (big) launch_linear_big<128, 128, 2, 2, EPH_QKV>(s, NI, a);
         else launch_linear_h<64, 192, 1, 3, EPH_QKV>(s, NI, a);  // 768 / 192 = 4 column tiles
     }
-    launch_attention_h(g, s, NI, qs, ks, vts, 0, fold);
+    launch_attention_h(g, s, plan, NI, qs, ks, vts, 0);
     ffn(0, l.w1, l.b1, l.lnw, l.lnb, l.w2, l.b2);
-    if (self_only) return false;
+    if (self_only) return;
     {   // cross block: the shared qk projection is both query and key -> sqrt(scale) on it
         LinearArgsH a = linh(g, act(xs, 0x10), none, D, D, D, l.cqkv, l.cbqkv, 2 * D);
         wgt(a, 0x40);
@@ -2270,9 +2243,8 @@ bool lg_layer_h(sslam_lightglue* g, hipStream_t s, int NI, const LGLayerW& l, in
         if (big) launch_linear_big<128, 128, 2, 2, EPH_CROSS>(s, NI, a);
         else launch_linear_h<64, 128, 1, 2, EPH_CROSS>(s, NI, a);
     }
-    launch_attention_h(g, s, NI, qs, qs, vts, 1, fold);
+    launch_attention_h(g, s, plan, NI, qs, qs, vts, 1);
     ffn(1, l.cw1, l.cb1, l.clnw, l.clnb, l.cw2, l.cb2);
-    return big && heads;
 }
 
 // Enqueue one batch of `pairs` pairs on the context stream.  `src` names the inputs of image
@@ -2283,11 +2255,12 @@ int lg_enqueue(sslam_lightglue* g, int pairs, const StageSrc& src, float min_con
     hipStream_t s = g->ctx->stream;
     (void)hipGetLastError();     // (a stale error of another library on this thread - e.g. RCCL's probes - is not ours)
     const int Kc = g->Kc, NI = 2 * pairs;
+    const LGPlan plan = sslam::lg_plan(g->hooks, Kc, NI, g->depth_conf > 0.0f || g->width_conf > 0.0f);
     hipLaunchKernelGGL(lg_prepare_kernel, dim3(NI, 8), dim3(1024), 0, s, src, Kc, g->in_xy, g->in_desc, g->bbox,
                        g->ind, g->prune, g->ctrl);
     hipLaunchKernelGGL(lg_posenc_kernel, dim3(sslam::cdiv(NI * Kc * ENC, 256)), dim3(256), 0, s, g->in_xy,
                        g->bbox, g->w_r, g->enc_cos, g->enc_sin, Kc, NI, g->ctrl);
-    const bool proj_h = g->precision == 1 && !g->sim_exact;       // the projections and the similarity GEMM on the split pipe
+    const bool proj_h = plan.proj_split;       // the projections and the similarity GEMM on the split pipe
     constexpr size_t big_lds = (size_t)sslam::BIG_STAGES * sslam::big_stage_halves<128, 128>() * sizeof(_Float16);
     const dim3 biggrid(D / 128, sslam::cdiv(Kc, 128), NI);
     if (proj_h) {   // input_proj: descriptors split into the (idle) k planes (k-panels), x and its planes from the epilogue
@@ -2307,17 +2280,16 @@ int lg_enqueue(sslam_lightglue* g, int pairs, const StageSrc& src, float min_con
     const unsigned tokblocks = sslam::cdiv(NI * Kc, 4);
     const dim3 headgrid(sslam::cdiv(Kc, 256), NI);               // one lane per token, one image per grid row
     const dim3 splitblocks(SPLIT_BLOCKS_PER_IMAGE, NI);
-    if (g->precision == 1 && !proj_h)
+    if (plan.split && !proj_h)
         hipLaunchKernelGGL(lg_split_rows_kernel, splitblocks, dim3(256), 0, s, g->x, g->xs_hi, g->xs_lo, D, Kc,
                            NI, g->NIc, g->ctrl, 0);
-    for (int i = 0; i < g->dbg_layers; ++i) {
+    for (int i = 0; i < plan.layers; ++i) {
         const LGLayerW& l = g->L[i];
-        const bool self_only = g->dbg_self_only && i == g->dbg_layers - 1;
-        // the token heads of this layer (early stop + pruning) ride in the cross block's fused FFN when there is one
-        const bool want_heads = !(i == NL - 1 || i == g->dbg_layers - 1) && (g->depth_conf > 0.0f || g->width_conf > 0.0f);
-        bool heads_done = false;
-        if (g->precision == 1) {
-            heads_done = lg_layer_h(g, s, NI, l, i, self_only, want_heads && g->big_gemm != 5);
+        const bool last = i == plan.layers - 1;
+        const bool self_only = plan.self_only_last && last;
+        if (plan.split) {
+            // the token heads of this layer (early stop + pruning) ride in the cross block's fused FFN when there is one
+            lg_layer_h(g, s, plan, NI, l, i, self_only, plan.heads_in_ffn && !last);
         } else {
             // ---- self block
             {
@@ -2325,7 +2297,7 @@ int lg_enqueue(sslam_lightglue* g, int pairs, const StageSrc& src, float min_con
                 a.q = g->q; a.k = g->k; a.v = g->v;
                 launch_linear<64, 128, 1, 2, EPI_QKV>(s, a);
             }
-            launch_attention(g, s, NI, g->q, g->k, g->v, 0);
+            launch_attention(g, s, plan, NI, g->q, g->k, g->v, 0);
             launch_ffn(g, s, NI, g->msg, l.w1, l.b1, l.lnw, l.lnb, l.w2, l.b2);
             if (!self_only) {
                 // ---- cross block
@@ -2334,17 +2306,17 @@ int lg_enqueue(sslam_lightglue* g, int pairs, const StageSrc& src, float min_con
                     a.q = g->q; a.v = g->v;
                     launch_linear<64, 128, 1, 2, EPI_CROSSQKV>(s, a);
                 }
-                launch_attention(g, s, NI, g->q, g->q, g->v, 1);
+                launch_attention(g, s, plan, NI, g->q, g->q, g->v, 1);
                 launch_ffn(g, s, NI, g->msg, l.cw1, l.cb1, l.clnw, l.clnb, l.cw2, l.cb2);
             }
         }
-        if (i == NL - 1 || i == g->dbg_layers - 1) break;
+        if (last) break;
         // ---- early stop + point pruning (lightglue.py check_if_stop / get_pruning_mask)
         const int do_stop = g->depth_conf > 0.0f;
         const int do_prune = g->width_conf > 0.0f;
         if (!do_stop && !do_prune) continue;
         const float thr = conf_threshold(i);
-        if (!heads_done)
+        if (!plan.heads_in_ffn)
             hipLaunchKernelGGL(lg_token_heads_kernel, headgrid, dim3(256), 0, s, g->x,
                                do_stop ? g->tc_w[i] : nullptr, do_stop ? g->tc_b[i] : nullptr,
                                g->mt_w + (size_t)i * g->mt_stride, g->mt_b + (size_t)i * g->mt_stride, 0L, 0,
@@ -2353,7 +2325,7 @@ int lg_enqueue(sslam_lightglue* g, int pairs, const StageSrc& src, float min_con
                            g->width_conf, g->prune_min, do_stop, g->conf, g->mat, g->ind, g->gmap,
                            g->prune, g->ctrl, Kc);
         if (do_prune) {
-            const bool sp = g->precision == 1;        // token rows moved: the copy back refreshes their split planes
+            const bool sp = plan.split;        // token rows moved: the copy back refreshes their split planes
             hipLaunchKernelGGL(lg_gather_kernel, dim3(tokblocks), dim3(256), 0, s, g->x, g->enc_cos,
                                g->enc_sin, g->gmap, g->tx, g->tc, g->ts, g->ctrl, Kc, NI, 0, nullptr, nullptr, g->NIc);
             hipLaunchKernelGGL(lg_gather_kernel, dim3(tokblocks), dim3(256), 0, s, g->x, g->enc_cos,
@@ -2469,8 +2441,8 @@ int sslam_lightglue_create_batched(sslam_ctx* ctx, const float* weights, size_t 
     const int Kc = (max_kpts + 127) / 128 * 128;     // whole attention / GEMM row blocks
     g->Kc = Kc;
     g->NB = max_pairs; g->NIc = 2 * max_pairs;
-    g->KSmax = Kc >= 1024 ? 4 : (Kc >= 512 ? 2 : 1);
-    if (const char* e = getenv("SSLAM_LG_SIM_EXACT")) g->sim_exact = e[0] == '1';
+    g->KSmax = sslam::lg_ks_max(Kc);
+    if (const char* e = getenv("SSLAM_LG_SIM_EXACT")) g->hooks.sim_exact = e[0] == '1';
     const size_t K = (size_t)Kc, NI = (size_t)g->NIc, NB = (size_t)max_pairs;
     auto carve = [&](sslam::Arena& A) {
         g->blob = A.take<float>(n_floats);
@@ -2736,8 +2708,7 @@ int sslam_lightglue_profile_read(sslam_lightglue* g, float* total_ms_out, int32_
 int sslam_lightglue_set_precision(sslam_lightglue* g, int mode) {
     SSLAM_REQUIRE(g != nullptr && (mode == 0 || mode == 1 || mode == 2), "sslam_lightglue_set_precision: bad argument");
     g->settings_changed();
-    g->precision = mode == 0 ? 0 : 1;
-    g->p_single = mode == 2;
+    g->hooks.precision = mode;
     return 0;
 }
 
@@ -2746,7 +2717,7 @@ int sslam_lightglue_set_precision(sslam_lightglue* g, int mode) {
 int sslam_lightglue_debug_layers(sslam_lightglue* g, int layers, int self_only) {
     SSLAM_REQUIRE(g != nullptr && layers >= 1 && layers <= NL, "sslam_lightglue_debug_layers: bad argument");
     g->settings_changed();
-    g->dbg_layers = layers; g->dbg_self_only = self_only != 0;
+    g->hooks.layers = layers; g->hooks.self_only = self_only != 0;
     return 0;
 }
 
@@ -2758,7 +2729,7 @@ int sslam_lightglue_debug_key_split(sslam_lightglue* g, int ks) {
                   "-1 (no split, r02 4-wave kernel), 0, 1, 2 or 4 (forced split, r02 4-wave kernel), 101, 102 or 104 (forced split, "
                   "assembly kernel)");
     g->settings_changed();
-    g->force_ks = ks;
+    g->hooks.key_split = ks;
     return 0;
 }
 
@@ -2767,7 +2738,7 @@ int sslam_lightglue_debug_key_split(sslam_lightglue* g, int ks) {
 int sslam_lightglue_debug_big_gemm(sslam_lightglue* g, int mode) {
     SSLAM_REQUIRE(g != nullptr && mode >= -1 && mode <= 5 && mode != 4, "sslam_lightglue_debug_big_gemm: bad argument");
     g->settings_changed();
-    g->big_gemm = mode;
+    g->hooks.big_gemm = mode;
     return 0;
 }
 
@@ -2787,7 +2758,7 @@ int sslam_lightglue_debug_split_form(sslam_lightglue* g, int mask) {
         SSLAM_HIP_CHECK(hipMalloc((void**)&g->zero_plane, n));
         SSLAM_HIP_CHECK(hipMemset(g->zero_plane, 0, n));
     }
-    g->study = mask;
+    g->hooks.study = mask;
     return 0;
 }
 
