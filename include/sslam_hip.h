@@ -186,6 +186,44 @@ int sslam_pnp_ransac_dev(sslam_ctx* ctx, int n_points, const int32_t* kp_of_poin
                          unsigned char* mask_out_dev, double* Tcw_out_dev, int32_t* n_out_dev,
                          int32_t* info_out_dev);
 
+/* ------------------------------------------------- two-view triangulation
+ * The numeric body of `triangulate_between_kfs_2view` (slam/core/triangulation_utils.py:143-271):
+ * `cv2.triangulatePoints` with P = K T[:3,:] (OpenCV 4.x's DLT, null vector by a one-sided Jacobi SVD of
+ * the 4 x 4 matrix itself), X = X4[:3] / w where w is finite and |w| > 1e-12, then the reference's gates
+ * in its order.  Every match gets one reason:
+ *   0 kept, 1 invalid_w, 2 low_parallax (only with use_parallax_gate: world-frame parallax < parallax_min_deg),
+ *   3 bad_depth (not min_depth <= z <= max_depth in both views), 4 behind_cam (z <= 1e-6 in a view),
+ *   5 high_reproj (max(e1, e2) > reproj_px_max).  fp64 throughout.
+ *   pts1, pts2 : float32 [n][2] matched pixels (host), used as doubles;  n == 0 is legal
+ *   K9 row-major 3x3;  T1_16, T2_16 : row-major 4x4 camera-from-world of the two views
+ *   X_out[n*3] : the kept points, compacted in match order;  idx_out[n] : their match indices
+ *   info_out[8] : kept, then the counts of reasons 0 .. 5, then n
+ *   reason_out[n] (may be NULL) : the reason per match;  diag_out[n*5] (may be NULL) : parallax in degrees
+ *   (NaN with the gate off), z1, z2, e1, e2 per match (+inf error behind a camera, NaN where w is invalid) */
+int sslam_triangulate_2view_host(sslam_ctx* ctx, int n, const float* pts1, const float* pts2,
+                                 const double* K9, const double* T1_16, const double* T2_16,
+                                 double min_depth, double max_depth, int use_parallax_gate,
+                                 double parallax_min_deg, double reproj_px_max, double* X_out,
+                                 int32_t* idx_out, int32_t* info_out, int32_t* reason_out,
+                                 double* diag_out);
+
+/* Device-resident form (enqueue only, no host round trip): consumes what `sslam_fmat_ransac_dev` left -
+ * the kept pairs ij_dev[*][2] and their count n_dev (its info[0]; clamped to [0, n_max], so a negative
+ * count is an empty input; NULL = exactly n_max) - on the keypoint arrays xy1_dev / xy2_dev [*][2] of the
+ * two frames.  T1_dev, T2_dev: DEVICE double[16] (a pose `sslam_pnp_ransac_dev` wrote can be passed as it
+ * is); K9 and the thresholds are host values.
+ *   X_out_dev[n_max*3], ij_out_dev[n_max][2] (may be NULL): the kept points and their (query, train) pairs,
+ *   in order;  info_out_dev[8] int32 as info_out above;  reason_out_dev[n_max] / diag_out_dev[n_max*5]
+ *   (may be NULL) as above
+ * The context's scratch buffer is (re)allocated when n_max grows: call once with the largest n_max
+ * before capturing or pipelining. */
+int sslam_triangulate_2view_dev(sslam_ctx* ctx, int n_max, const int32_t* n_dev, const float* xy1_dev,
+                                const float* xy2_dev, const int32_t* ij_dev, const double* K9,
+                                const double* T1_dev, const double* T2_dev, double min_depth,
+                                double max_depth, int use_parallax_gate, double parallax_min_deg,
+                                double reproj_px_max, double* X_out_dev, int32_t* ij_out_dev,
+                                int32_t* info_out_dev, int32_t* reason_out_dev, double* diag_out_dev);
+
 /* ------------------------------------------- 2D-3D association for tracking
  * Replaces the per-point loop of `reproject_and_match_2d3d` (slam/core/pnp_utils.py:224-304) for
  * float descriptors: projection (`_project_points` :127-141), radius search (cKDTree :238, :265),

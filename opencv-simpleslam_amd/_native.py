@@ -61,6 +61,10 @@ def _signatures():
         "sslam_fmat_ransac_dev": (i32, [vp, i32, vp, vp, vp, vp, C.c_double, C.c_double, i32, vp, vp, vp, vp]),
         "sslam_pnp_ransac_host": (i32, [vp, i32, vp, vp, vp, vp, C.c_double, C.c_double, i32, vp, vp, vp]),
         "sslam_pnp_ransac_dev": (i32, [vp, i32, vp, vp, vp, vp, vp, C.c_double, C.c_double, i32, vp, vp, vp, vp]),
+        "sslam_triangulate_2view_host": (i32, [vp, i32, vp, vp, vp, vp, vp, C.c_double, C.c_double, i32, C.c_double, C.c_double,
+                                               vp, vp, vp, vp, vp]),
+        "sslam_triangulate_2view_dev": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, i32, C.c_double,
+                                              C.c_double, vp, vp, vp, vp, vp]),
         "sslam_reproject_match_host": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, C.c_double, C.c_double,
                                              vp, vp, vp]),
         "sslam_reproject_match_dev": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, C.c_double, C.c_double,
