@@ -109,7 +109,7 @@ def _isa_guard():
 def build_native(force: bool = False, verbose: bool = False) -> Path:
     """Incremental build keyed on CONTENT, not mtimes: an object is reused only if its key file
     holds the hash of (compiler, flags, extra flags, the source, every header).  So an experiment
-    build (SSLAM_EXTRA_HIPCC_FLAGS=-DSSLAM_DBG_NOMFMA=1 ...) can never survive into a default build,
+    build (SSLAM_EXTRA_HIPCC_FLAGS=-O2 ...) can never survive into a default build,
     a source edit always rebuilds, and a snapshot copy that scrambles mtimes rebuilds nothing."""
     hipcc = _hipcc()
     LIB_DIR.mkdir(exist_ok=True)
@@ -120,10 +120,11 @@ def build_native(force: bool = False, verbose: bool = False) -> Path:
     if not sources:
         raise RuntimeError(f"no .hip sources under {CSRC}")
 
-    extra = os.environ.get("SSLAM_EXTRA_HIPCC_FLAGS", "").split()     # experiments only (e.g. -DSSLAM_DBG=1)
+    extra = os.environ.get("SSLAM_EXTRA_HIPCC_FLAGS", "").split()     # experiments only (compiler flags of an A/B script)
     if extra and os.environ.get("SSLAM_EXPERIMENT_BUILD") != "1":
-        # the ablation switches in csrc/ (FFN_ABL, SSLAM_DBG_NOMFMA, AL_B2_ASM, AL_AGG_FAST_SELU ...) change ARITHMETIC: a flag
-        # variable left in the environment must not leak into a product build.  The A/B scripts under scripts/ say so.
+        # csrc/ has no build switches of its own any more (tests/test_no_build_switches.py), but a compiler flag can still change
+        # ARITHMETIC or the code shapes isa_guard vouches for: a flag variable left in the environment must not leak into a
+        # product build.  The A/B scripts under scripts/ say so.
         raise RuntimeError(f"SSLAM_EXTRA_HIPCC_FLAGS={' '.join(extra)!r} is set but SSLAM_EXPERIMENT_BUILD is not 1: refusing to build "
                            "the product library with experiment flags (unset the variable, or export SSLAM_EXPERIMENT_BUILD=1 "
                            "for an A/B run under scripts/)")

@@ -33,19 +33,12 @@ constexpr float SELU_SCALE = 1.0507009873554804934193349852946f;
 constexpr float SELU_ALPHA = 1.6732632423543772848170429916717f;
 // (r04: a ~18-instruction expm1 - Taylor near zero, exact-argument exp2 below - instead of ocml's expm1f changed no kernel's
 //  time by more than 4 %: these kernels wait on memory, their vector pipe is not the limit; ocml's stays)
-#ifndef AL_FAST_SELU
-#define AL_FAST_SELU 1
-#endif
 // SELU.  r04: exp(x) - 1 on the hardware exponential (v_exp_f32, 1 ulp) instead of expm1f - 7 instead of ~30 vector instructions
 // per value; the dense stages are bound by vector-instruction issue (the aggregation evaluates 40 SELUs per pixel, the
 // descriptor GEMM epilogue 4 M per frame).  Absolute error <= 1.2e-7 x 1.76 (the subtraction near x = 0): fp32 rounding of an
-// O(1) value.  AL_FAST_SELU=0 restores expm1f.
+// O(1) value.
 __device__ __forceinline__ float selu(float x) {
-#if AL_FAST_SELU
     return SELU_SCALE * (x > 0.0f ? x : SELU_ALPHA * (__expf(x) - 1.0f));
-#else
-    return SELU_SCALE * (x > 0.0f ? x : SELU_ALPHA * expm1f(x));
-#endif
 }
 
 // SELU on ocml's expm1f (a polynomial + v_ldexp: no transcendental instruction): al_aggregate_kernel keeps it.  History: with
@@ -59,13 +52,7 @@ __device__ __forceinline__ float selu(float x) {
 // on the same SIMD (scripts/ubench/pk_probe.hip reproduces it in a 60-line kernel).  The kernel now carries no packed fp32 at all
 // (AL_AGG_TARGET below) and build.py refuses any library that holds the form (isa_guard.py); the polynomial SELU stays because
 // the kernel is latency-bound (no time difference) and its outputs are the ones every golden hash was taken with.
-#ifndef AL_AGG_FAST_SELU
-#define AL_AGG_FAST_SELU 0
-#endif
-// (AL_AGG_FAST_SELU, experiments only - scripts/ab_stress_aliked.sh: bit 0 = the hardware-exponential form in the kernel's channel
-//  loop, bit 1 = in its tail)
-template <int SITE> __device__ __forceinline__ float selu_precise(float x) {
-    if ((AL_AGG_FAST_SELU >> SITE) & 1) return selu(x);
+__device__ __forceinline__ float selu_precise(float x) {
     return SELU_SCALE * (x > 0.0f ? x : SELU_ALPHA * expm1f(x));
 }
 constexpr int HBINS = 4096;        // score histogram bins (uniform in score, monotone)
@@ -123,26 +110,15 @@ template <typename T> __device__ __forceinline__ T* fsh(T* p, int f, size_t fs) 
 // unchanged within 2 %: neither kernel is bound by that traffic - scripts/ab_aliked_band.sh; form 1, whole frames per XCD at
 // F = 8, measured 2 % slower per call).  Placement only: every tile is computed by exactly one workgroup with the same arithmetic.
 // -> (x, y, z) the kernel uses in place of blockIdx.
-#ifndef AL_XCD_BAND
-#define AL_XCD_BAND 2
-#endif
 struct Tile3 { int x, y, z; };
 __device__ __forceinline__ Tile3 xcd_band() {
-#if AL_XCD_BAND == 1
-    const unsigned nx = gridDim.x, ny = gridDim.y, total = nx * ny * gridDim.z;
-    if ((total & 7u) == 0u) {
-        const unsigned L = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
-        const unsigned g = (L & 7u) * (total >> 3) + (L >> 3);
-        return Tile3{(int)(g % nx), (int)((g / nx) % ny), (int)(g / (nx * ny))};
-    }
-#elif AL_XCD_BAND == 2          // bands inside every frame (the XCDs work on the same frame at the same time)
+    // bands inside every frame (the XCDs work on the same frame at the same time)
     const unsigned nx = gridDim.x, ny = gridDim.y, per = nx * ny;
     if ((per & 7u) == 0u) {
         const unsigned L = blockIdx.x + nx * blockIdx.y;
         const unsigned g = (L & 7u) * (per >> 3) + (L >> 3);
         return Tile3{(int)(g % nx), (int)(g / nx), (int)blockIdx.z};
     }
-#endif
     return Tile3{(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z};
 }
 template <typename T> __device__ __forceinline__ T* fsh0(T* p, int f, size_t fs) {      // null stays null (run-time optional outputs)
@@ -288,57 +264,33 @@ __global__ void al_conv32_wfrag_kernel(const float* __restrict__ w /*[ci 32][tap
 //      pixels = the strip + one on each side, 32 channels), both channel-last fp16 (hi, lo).  Step y: prefetch the input of
 //      pooled row y + 3; conv1 -> t2 row y + 1 (zero outside the map: conv2's padding) into the t2 ring; the 1 x 1 branch on
 //      pooled row y; conv2 row y from the t2 ring; + BN + residual + SELU -> x2 (planar fp32).  Split-precision matrix path
-//      throughout (3 x (27 + 3 + 54) v_mfma_f32_32x32x16_f16 per step).  Four independent waves per workgroup share the A
-//      fragments in LDS (conv1 lo planes 10 KB, conv2 36 KB; conv1 hi planes in registers): 147 KB, one workgroup per CU,
-//      no workgroup barrier after the weights are staged.
+//      throughout (3 x (27 + 3 + 54) v_mfma_f32_32x32x16_f16 per step).  Four independent waves per workgroup, every A fragment
+//      in registers: one workgroup per CU, no workgroup barrier after the affine tables are staged.
 // ------------------------------------------------------------------------ //
 constexpr int B2_SW = 30;                                   // output pixels per strip
 constexpr int B2_PXP = 24, B2_ROWP = 34 * B2_PXP, B2_PLP = 3 * B2_ROWP;          // pooled ring (halves)
 constexpr int B2_PXT = 40, B2_ROWT = 32 * B2_PXT, B2_PLT = 3 * B2_ROWT;          // t2 ring (halves)
 constexpr int B2_RING = 2 * B2_PLP + 2 * B2_PLT;                                   // halves per wave
-#ifndef AL_B2_WREG
-#define AL_B2_WREG 1       // 1: every A fragment in registers (224 of the wave's 512; one wave per SIMD either way) - the LDS then only serves B fragments
-#endif
-constexpr int B2_W1 = AL_B2_WREG ? 0 : 10 * 64 * 8, B2_W2 = AL_B2_WREG ? 0 : 36 * 64 * 8;      // shared A fragments (halves)
-constexpr size_t B2_LDS = (size_t)(B2_W1 + B2_W2 + 4 * B2_RING) * 2 + 5 * 32 * 4;
+// every A fragment in registers (224 of the wave's 512; one wave per SIMD either way) - the LDS only serves B fragments
+constexpr size_t B2_LDS = (size_t)(4 * B2_RING) * 2 + 5 * 32 * 4;
 
-#ifndef AL_B2_ASM
-#define AL_B2_ASM 1
-#endif
 // The 224 registers of A fragments live in the accumulation-register file: written once, read by the MFMAs directly.  Through the
 // builtin the compiler copies each fragment to an arch register first (257 v_accvgpr_read per step) and zeroes every chain's
 // accumulator with 16 moves; here the first MFMA of a chain takes the literal 0 as C.  An asm MFMA is opaque to the hazard
 // recogniser: nothing writes the A registers inside the loop, B fragments arrive by ds_read (waited for by register use), and
 // b2_mfma_done(c1, c2) pads the MFMA -> VALU read distance after the last MFMA of a chain (as an in/out of both accumulators).
-#if AL_B2_ASM && AL_B2_WREG
 #define B2_AREG "a"
-#else
-#define B2_AREG "v"
-#endif
 __device__ __forceinline__ void b2_mfma0(f32x16& c, const sslam::half8& a_, const sslam::half8& b_) {
-#if AL_B2_ASM
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(c) : B2_AREG(a_), "v"(b_));
-#else
-    f32x16 z;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) z[r] = 0.0f;
-    c = sslam::mfma16(a_, b_, z);
-#endif
 }
 __device__ __forceinline__ void b2_mfma(f32x16& c, const sslam::half8& a_, const sslam::half8& b_) {
-#if AL_B2_ASM
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c) : B2_AREG(a_), "v"(b_));
-#else
-    c = sslam::mfma16(a_, b_, c);
-#endif
 }
 __device__ __forceinline__ void b2_mfma_done(f32x16& c1, f32x16& c2) {
-#if AL_B2_ASM
     // the 19 wait states between the last MFMA of a chain and the first vector read of its accumulators, TIED to the
     // accumulators: every later read of c1 / c2 depends on this statement's outputs, so the compiler cannot schedule one
     // between the (opaque) MFMA statements and the padding
     asm volatile("s_nop 15\n\ts_nop 3" : "+v"(c1), "+v"(c2));
-#endif
 }
 __global__ __launch_bounds__(256, 1) void al_block2_rows_kernel(const float* __restrict__ in /* x1 [16][2 H][2 W] */, float* __restrict__ out /* x2 [32][H][W] */,
                                                                int H, int W, int hs, int nblk, int strips, int n_waves,
@@ -346,16 +298,11 @@ __global__ __launch_bounds__(256, 1) void al_block2_rows_kernel(const float* __r
                                                                const float* __restrict__ a1, const float* __restrict__ b1, const float* __restrict__ bd,
                                                                const float* __restrict__ a2, const float* __restrict__ b2, ALCtrl* ctrl, size_t fs) {
     extern __shared__ __attribute__((aligned(16))) unsigned char b2_lds[];
-    _Float16* w1lo = reinterpret_cast<_Float16*>(b2_lds);
-    _Float16* w2 = w1lo + B2_W1;
-    float* aff = reinterpret_cast<float*>(w2 + B2_W2 + 4 * B2_RING);
+    _Float16* rings = reinterpret_cast<_Float16*>(b2_lds);
+    float* aff = reinterpret_cast<float*>(rings + 4 * B2_RING);
     // (the wave index as a SCALAR: strip, block, frame and every row pointer derived from it stay in scalar registers)
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), h = lane >> 5, px = lane & 31;
-    // stage the shared A fragments and the affine tables
-    for (int i = t; i < B2_W1 / 8; i += 256)
-        *reinterpret_cast<uint4*>(w1lo + i * 8) = *reinterpret_cast<const uint4*>(wf1 + (((i >> 6) * 2 + 1) * 64 + (i & 63)) * 8);
-    for (int i = t; i < B2_W2 / 8; i += 256) *reinterpret_cast<uint4*>(w2 + i * 8) = *reinterpret_cast<const uint4*>(wf2 + (size_t)i * 8);
-    (void)w1lo;
+    // stage the affine tables
     if (t < 32) { aff[t] = a1[t]; aff[32 + t] = b1[t]; aff[64 + t] = bd[t]; aff[96 + t] = a2[t]; aff[128 + t] = b2[t]; }
     __syncthreads();
     const int gw = blockIdx.x * 4 + wave;
@@ -363,7 +310,7 @@ __global__ __launch_bounds__(256, 1) void al_block2_rows_kernel(const float* __r
     const int strip = gw % strips, blk = (gw / strips) % nblk, f = gw / (strips * nblk);
     in = fsh(in, f, fs); out = fsh(out, f, fs); ctrl = fsh(ctrl, f, fs);
     float amax = 0.0f;                                       // largest magnitude this thread split (al_range_note at the end)
-    _Float16* P = w2 + B2_W2 + wave * B2_RING;               // [plane][slot][34][24]
+    _Float16* P = rings + wave * B2_RING;                    // [plane][slot][34][24]
     _Float16* T = P + 2 * B2_PLP;                            // [plane][slot][32][40]
     const int x0 = strip * B2_SW, yb = blk * hs, ye = min(yb + hs, H);
     const int inW = 2 * W, inH = 2 * H;
@@ -371,7 +318,6 @@ __global__ __launch_bounds__(256, 1) void al_block2_rows_kernel(const float* __r
     sslam::half8 ah1[10];
 #pragma unroll
     for (int ks = 0; ks < 10; ++ks) ah1[ks] = *reinterpret_cast<const sslam::half8*>(wf1 + ((ks * 2 + 0) * 64 + lane) * 8);
-#if AL_B2_WREG
     sslam::half8 al1[10], wr2[36];
 #pragma unroll
     for (int ks = 0; ks < 10; ++ks) al1[ks] = *reinterpret_cast<const sslam::half8*>(wf1 + ((ks * 2 + 1) * 64 + lane) * 8);
@@ -379,12 +325,6 @@ __global__ __launch_bounds__(256, 1) void al_block2_rows_kernel(const float* __r
     for (int i = 0; i < 36; ++i) wr2[i] = *reinterpret_cast<const sslam::half8*>(wf2 + (i * 64 + lane) * 8);
 #define B2_A1LO(ks) al1[ks]
 #define B2_A2(i) wr2[i]
-#else
-    const _Float16* w1l = w1lo + lane * 8;
-    const _Float16* w2l = w2 + lane * 8;
-#define B2_A1LO(ks) (*reinterpret_cast<const sslam::half8*>(w1l + (ks) * 512))
-#define B2_A2(i) (*reinterpret_cast<const sslam::half8*>(w2l + (i) * 512))
-#endif
     // a pooled row = 16 channels x 17 float4 pairs (34 pooled pixels from x0 - 2): 272 items, five rounds
     unsigned iofs[5]; bool iok[5]; int ipo[5];
 #pragma unroll
@@ -1068,9 +1008,7 @@ __device__ __forceinline__ float up_eval(const float* __restrict__ p, const UpTa
 // (neighbours clamped at the border, where their tap weight is exactly zero).  One thread per level pixel, all three levels
 // of a frame in one launch; reads the planar levels.
 constexpr int AGG_PRE = 13;
-#ifndef AL_PRE_UNROLL
-#define AL_PRE_UNROLL 32       // all 128 loads of a thread in flight at once: 5.4 us per frame (rounds of 8 / 16 channels: 11.3 / 18.5 - a memory latency per round)
-#endif
+constexpr int PRE_UNROLL = 32;        // all 128 loads of a thread in flight at once: 5.4 us per frame (rounds of 8 / 16 channels: 11.3 / 18.5 - a memory latency per round)
 __global__ __launch_bounds__(256) void al_agg_pre_kernel(const float* __restrict__ g2cl /* planar [32][pixels] */, const float* __restrict__ g3cl,
                                                          const float* __restrict__ g4cl, const float* __restrict__ ws0 /*[128][8]*/,
                                                          float* __restrict__ pre2, float* __restrict__ pre3, float* __restrict__ pre4,
@@ -1094,7 +1032,7 @@ __global__ __launch_bounds__(256) void al_agg_pre_kernel(const float* __restrict
     const float* w = ws0 + lvl * 32 * 8;
     // planar reads: lane = pixel, so one load instruction is 256 contiguous bytes per channel (the channel-last copies
     // would make every lane fetch its own 128-byte line: 22 us per frame measured, this form ~3)
-#pragma unroll AL_PRE_UNROLL
+#pragma unroll PRE_UNROLL
     for (int c = 0; c < 32; ++c) {
         const float* gc = g + (size_t)c * n;
         const float av = gc[ia], bv = gc[ib], cv = gc[ic], dv = gc[id];
@@ -1109,9 +1047,6 @@ __global__ __launch_bounds__(256) void al_agg_pre_kernel(const float* __restrict
     pre[(size_t)11 * n + i] = d1; pre[(size_t)12 * n + i] = d2;
 }
 
-#if defined(AL_AGG_LOAD_NOP) && AL_AGG_LOAD_NOP == 3
-__device__ unsigned al_dbg_words[64];       // experiment only (sslam_aliked_debug_read(99)): see agg_level
-#endif
 // contribution of one upsampled level at a full-resolution pixel: s[o] += up(proj[o]), n2 += the quadratic form
 __device__ __forceinline__ void agg_level(const float* __restrict__ pre, int n, const UpTap& t, float (&s)[8], float& n2) {
 #pragma unroll
@@ -1119,80 +1054,22 @@ __device__ __forceinline__ void agg_level(const float* __restrict__ pre, int n, 
     const float w00 = t.w10 * t.w00, w01 = t.w10 * t.w01, w10 = t.w11 * t.w00, w11 = t.w11 * t.w01;     // hy hx, hy lx, ly hx, ly lx
     const float* S = pre + (size_t)8 * n; const float* H = pre + (size_t)9 * n; const float* V = pre + (size_t)10 * n;
     const float* D1 = pre + (size_t)11 * n; const float* D2 = pre + (size_t)12 * n;
-#ifdef AL_AGG_LOAD_NOP
-    // experiment (scripts/diag_agg_rnorm.sh, profiles/r06_aggregate_rnorm_diagnosis.md): the ten gathers of the quadratic form
-    // in named registers and an asm statement that reads them all - the compiler's s_waitcnt vmcnt lands in FRONT of it - with
-    // (1) or without (2) idle cycles before the first instruction that consumes a loaded register
-    float s00 = S[t.o00], s01 = S[t.o01], s10 = S[t.o10], s11 = S[t.o11], h00 = H[t.o00], h10 = H[t.o10], v00 = V[t.o00],
-          v01 = V[t.o01], d1 = D1[t.o00], d2 = D2[t.o00];
-#if AL_AGG_LOAD_NOP == 1
-    asm volatile("s_nop 7" : "+v"(s00), "+v"(s01), "+v"(s10), "+v"(s11), "+v"(h00), "+v"(h10), "+v"(v00), "+v"(v01), "+v"(d1), "+v"(d2));
-#else
-    asm volatile("" : "+v"(s00), "+v"(s01), "+v"(s10), "+v"(s11), "+v"(h00), "+v"(h10), "+v"(v00), "+v"(v01), "+v"(d1), "+v"(d2));
-#endif
-    const float sq = (w00 * w00 * s00 + w01 * w01 * s01) + (w10 * w10 * s10 + w11 * w11 * s11);
-#if AL_AGG_LOAD_NOP == 3
-    // (3): is it the LOADED REGISTER that holds a wrong value, or the packed instruction that consumes it?  The six cross products
-    // once as the compiler forms them (SLP-vectorised: v_pk_mul_f32 on register pairs) and once by single-lane-width v_mul_f32 in
-    // inline assembly ON THE SAME REGISTERS (coefficients laundered through an asm so both forms read the same six values);
-    // a lane whose two forms disagree records itself in al_dbg_words
-    float c0 = w00 * w01, c1 = w10 * w11, c2 = w00 * w10, c3 = w01 * w11, c4 = w00 * w11, c5 = w01 * w10;
-    asm volatile("" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3), "+v"(c4), "+v"(c5));
-    const float p0 = c0 * h00, p1 = c1 * h10, p2 = c2 * v00, p3 = c3 * v01, p4 = c4 * d1, p5 = c5 * d2;
-    float q0, q1, q2, q3, q4, q5;
-    asm volatile("v_mul_f32 %0, %6, %12\n\tv_mul_f32 %1, %7, %13\n\tv_mul_f32 %2, %8, %14\n\tv_mul_f32 %3, %9, %15\n\t"
-                 "v_mul_f32 %4, %10, %16\n\tv_mul_f32 %5, %11, %17"
-                 : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3), "=&v"(q4), "=&v"(q5)
-                 : "v"(c0), "v"(c1), "v"(c2), "v"(c3), "v"(c4), "v"(c5), "v"(h00), "v"(h10), "v"(v00), "v"(v01), "v"(d1), "v"(d2));
-    const float cr = ((p0 + p1) + (p2 + p3)) + (p4 + p5);
-    {
-        const int differ = (p0 != q0) | ((p1 != q1) << 1) | ((p2 != q2) << 2) | ((p3 != q3) << 3) | ((p4 != q4) << 4) | ((p5 != q5) << 5);
-        if (differ) {
-            const unsigned k = atomicAdd(&al_dbg_words[0], 1u);
-            atomicOr(&al_dbg_words[1], (unsigned)differ);                         // which of the six products ever differed
-            atomicOr(&al_dbg_words[2], 1u << ((threadIdx.x & 63) >> 4));          // which 16-lane group of the wave
-            if (k < 8) {                                                          // the first few in full: packed, scalar, both operands
-                const float pv[6] = {p0, p1, p2, p3, p4, p5}, qv[6] = {q0, q1, q2, q3, q4, q5}, cv[6] = {c0, c1, c2, c3, c4, c5},
-                            gv[6] = {h00, h10, v00, v01, d1, d2};
-                const int w = __ffs(differ) - 1;
-                unsigned* o = al_dbg_words + 8 + 6 * k;
-                o[0] = (unsigned)differ | ((threadIdx.x & 63) << 8) | ((unsigned)n << 16);
-                o[1] = __float_as_uint(pv[w]); o[2] = __float_as_uint(qv[w]); o[3] = __float_as_uint(cv[w]); o[4] = __float_as_uint(gv[w]);
-                o[5] = blockIdx.x | (blockIdx.y << 8) | (blockIdx.z << 24);
-            }
-        }
-    }
-#else
-    const float cr = ((w00 * w01) * h00 + (w10 * w11) * h10) + ((w00 * w10) * v00 + (w01 * w11) * v01) +
-                     ((w00 * w11) * d1 + (w01 * w10) * d2);
-#endif
-#else
     const float sq = (w00 * w00 * S[t.o00] + w01 * w01 * S[t.o01]) + (w10 * w10 * S[t.o10] + w11 * w11 * S[t.o11]);
     const float cr = ((w00 * w01) * H[t.o00] + (w10 * w11) * H[t.o10]) + ((w00 * w10) * V[t.o00] + (w01 * w11) * V[t.o01]) +
                      ((w00 * w11) * D1[t.o00] + (w01 * w10) * D2[t.o00]);
-#endif
     n2 += fmaf(2.0f, cr, sq);
 }
 
 // (r03: the kernel is latency-bound - waves parked 65 % of their cycles, SQ counters - so the level loops carry four
 //  channels = 16 gathers in flight per iteration: 49 -> 40 us per frame; eight: the weights start to spill to v_readlane)
-#ifndef AL_AGG1_UNROLL
-#define AL_AGG1_UNROLL 2
-#endif
-// r06: NO packed-fp32 instructions in this kernel (AL_AGG_PACKED=1 lifts that, for the experiment scripts only).  Its one known
+constexpr int AGG1_UNROLL = 2;
+// r06: NO packed-fp32 instructions in this kernel.  Its one known
 // fault - 1 / ||F|| wrong by 0.2 - 4 % in lanes 48..63 of a wave, once per few hundred frames and only with other streams'
 // kernels on the GPU - was n2 missing the D2 term of one level's quadratic form because its coefficient hy lx came out 0.0 of
 // `v_pk_mul_f32 ... op_sel:[0,1]` (see selu_precise above; bisected in the compiler's own assembly, one instruction at a time:
 // scripts/agg_isa_patch.py).  Whether the vectoriser forms that instruction depended on an unrelated detail (the exponential of
 // the tail); the attribute takes the choice away from it, and isa_guard.py checks every kernel of every build for the form.
-#ifndef AL_AGG_PACKED
-#define AL_AGG_PACKED 0
-#endif
-#if AL_AGG_PACKED
-#define AL_AGG_TARGET
-#else
 #define AL_AGG_TARGET __attribute__((target("no-packed-fp32-ops")))
-#endif
 AL_AGG_TARGET __global__ __launch_bounds__(256) void al_aggregate_kernel(Pyr P0, const float* __restrict__ ws0 /*[128][8]*/,
                                                            float* __restrict__ s8, float* __restrict__ rnorm, size_t fs) {
     const Pyr P = pyr_at(P0, blockIdx.z, fs);
@@ -1210,14 +1087,14 @@ AL_AGG_TARGET __global__ __launch_bounds__(256) void al_aggregate_kernel(Pyr P0,
 #pragma unroll
     for (int o = 0; o < 8; ++o) s[o] = 0.0f;
     float n2 = 0.0f;
-    // channel loops stay rolled (AL_AGG1_UNROLL channels per iteration): fully unrolled, their wave-uniform
+    // channel loops stay rolled (AGG1_UNROLL channels per iteration): fully unrolled, their wave-uniform
     // weights overflow the SGPR file and return through v_readlane
-#pragma unroll AL_AGG1_UNROLL
+#pragma unroll AGG1_UNROLL
     for (int c = 0; c < 32; ++c) {
         float a = 0.0f;
 #pragma unroll
         for (int k = 0; k < 16; ++k) a = fmaf(xv[k], P.w1[k * 32 + c], a);
-        a = selu_precise<0>(a);
+        a = selu_precise(a);
         g1s[threadIdx.x * 33 + c] = a;     // the descriptor head gathers this instead of redoing the 16x32 product
         n2 = fmaf(a, a, n2);
 #pragma unroll
@@ -1229,17 +1106,9 @@ AL_AGG_TARGET __global__ __launch_bounds__(256) void al_aggregate_kernel(Pyr P0,
     agg_level(P.pre3, (int)(HW / 64), t3, s, n2);
     agg_level(P.pre4, (int)(HW / 1024), t4, s, n2);
     if (live) {
-#if (AL_AGG_FAST_SELU >> 2) & 1          // (experiment: the norm first, the eight exponentials of the tail behind it)
-        rnorm[pix] = 1.0f / fmaxf(sqrtf(n2), 1e-12f);
-#endif
 #pragma unroll
-        for (int o = 0; o < 8; ++o) s8[o * HW + pix] = selu_precise<1>(s[o]);
-#if (AL_AGG_FAST_SELU >> 3) & 1          // (experiment: 32 idle cycles between the last exponential's chain and the square root)
-        asm volatile("s_nop 15\n\ts_nop 15" : "+v"(n2));
-#endif
-#if !((AL_AGG_FAST_SELU >> 2) & 1)
+        for (int o = 0; o < 8; ++o) s8[o * HW + pix] = selu_precise(s[o]);
         rnorm[pix] = 1.0f / fmaxf(sqrtf(n2), 1e-12f);            // F.normalize eps
-#endif
     }
     // (the header's inline functions - __syncthreads, make_float4 - are compiled with the file's target features and would stay
     //  CALLS from a kernel whose features differ: the barrier and the 16-byte store are written with the builtins they wrap)
@@ -1309,10 +1178,7 @@ __device__ __forceinline__ float2 feat_pair32(const Pyr& P, const float* __restr
 //  4. score head tail: 3x3 (8->4) SELU, 3x3 (4->4) SELU, 3x3 (4->1), sigmoid.
 //     One kernel, intermediate layers kept in LDS; zero padding at the padded-map border.
 // ------------------------------------------------------------------------ //
-#ifndef AL_ST_H
-#define AL_ST_H 8
-#endif
-constexpr int ST_W = 32, ST_H = AL_ST_H;
+constexpr int ST_W = 32, ST_H = 8;
 
 __global__ __launch_bounds__(256) void al_score_tail_kernel(const float* __restrict__ s8, int Hp, int Wp,
                                                             const float* __restrict__ w2 /*[8][9][4]*/,
@@ -1396,10 +1262,7 @@ constexpr int NHALO = 10;     // dependency radius of simple_nms: 2 + 4 + 4
 // float map (r03 form: 3.7 x halo redundancy, ~60 LDS operations per element, 9.6 us per frame; max is exact and
 // associative, so the order of the pooling steps changes nothing: nms is bit-identical.  block_sum's partition changes, i.e.
 // the rounding of the mean score the no-candidate fallback thresholds on).
-#ifndef AL_NMS_ROWS
-#define AL_NMS_ROWS 48
-#endif
-constexpr int NW_R = AL_NMS_ROWS, NW_OW = 64 - 2 * NHALO, NW_OH = NW_R - 2 * NHALO;
+constexpr int NW_R = 48, NW_OW = 64 - 2 * NHALO, NW_OH = NW_R - 2 * NHALO;
 static_assert(NW_R <= 64 && NW_OH > 0, "a column's rows are the bits of one 64-bit word");
 
 // lane i <- lane i - 1 / lane i + 1; the wave's first / last lane reads 0 (bound_ctrl): the identity of the mask ORs, and for the
@@ -1909,8 +1772,8 @@ __global__ __launch_bounds__(256) void al_sample_kernel(Pyr P0, const float* __r
     // r04: the four corners are neighbours at full resolution, so on the 1/8 and 1/32 levels they almost always (77 % / 94 %) read
     // the SAME four source pixels with different weights: those taps are then loaded once (4 instead of 16 gathers per level;
     // the kernel sits at ~55 % of the texture-address rate; 20 -> 18 us per frame).  Same taps, same weights, same mix per corner;
-    // -DAL_SAMPLE_SHARED=0 builds the per-corner loads only (the two builds agree to 1.5e-7 on the unit descriptors, i.e. to the
-    // contractions the compiler picks around the mix, and share keypoints and scores bit for bit).
+    // a build with the per-corner loads only agrees with this one to 1.5e-7 on the unit descriptors, i.e. to the
+    // contractions the compiler picks around the mix, and shares keypoints and scores bit for bit.
     unsigned pixq[4]; UpTap t2[4], t3[4], t4[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -1923,9 +1786,6 @@ __global__ __launch_bounds__(256) void al_sample_kernel(Pyr P0, const float* __r
         t3[q] = up_tap(yp, xp, P.Hp, P.Wp, 8, P.sy8, P.sx8);
         t4[q] = up_tap(yp, xp, P.Hp, P.Wp, 32, P.sy32, P.sx32);
     }
-#ifndef AL_SAMPLE_SHARED
-#define AL_SAMPLE_SHARED 1
-#endif
     auto same_taps = [](const UpTap (&t)[4]) {
         bool s_ = true;
 #pragma unroll
@@ -1934,7 +1794,7 @@ __global__ __launch_bounds__(256) void al_sample_kernel(Pyr P0, const float* __r
     };
     const unsigned cbo = 4u * (lane & 31);
     auto level_shared = [&](const float* __restrict__ p, const UpTap (&t)[4], float (&o)[4]) {
-        if (AL_SAMPLE_SHARED && same_taps(t)) {
+        if (same_taps(t)) {
             const float v00 = at_b(p, (unsigned)t[0].o00 * 128u + cbo), v01 = at_b(p, (unsigned)t[0].o01 * 128u + cbo);
             const float v10 = at_b(p, (unsigned)t[0].o10 * 128u + cbo), v11 = at_b(p, (unsigned)t[0].o11 * 128u + cbo);
 #pragma unroll
@@ -2256,21 +2116,17 @@ int al_enqueue(sslam_aliked* g, int F, const FrameIn& srcs, int H, int W, int C,
         hipLaunchKernelGGL(al_block2_rows_kernel, dim3(sslam::cdiv(n_waves, 4)), dim3(256), B2_LDS, s, g->x1, g->x2, H2, W2, hs2, nb, strips, n_waves,
                            g->b2c1f, g->b2c2f, g->b2c1.a, g->b2c1.b, g->b2db, g->b2c2.a, g->b2c2.b, g->ctrl, fs);
     }
-#ifndef AL_DCN4_CS
-#define AL_DCN4_CS 4      // workgroups per pixel tile of the 1/32 deformable layers (output channels split: 10 tiles per frame there)
-#endif
-#ifndef AL_DCN3_CS
-#define AL_DCN3_CS 1
-#endif
+    constexpr int DCN4_CS = 4;      // workgroups per pixel tile of the 1/32 deformable layers (output channels split: 10 tiles per frame there)
+    constexpr int DCN3_CS = 1;
     // block3 at 1/8 (deformable): per layer the offset conv, then sampling + contraction + BN (+ 1 x 1 residual branch) + SELU fused
     const int H3 = Hp / 8, W3 = Wp / 8, HW3 = H3 * W3;
     const dim3 g3(sslam::cdiv(W3, 32), H3, uF);
     hipLaunchKernelGGL(al_avgpool_kernel, dim3(sslam::cdiv(32 * HW3, 256), uF), dim3(256), 0, s, g->x2, g->p3, 32, H2, W2, 4, fs, g->p3cl);
     const float mo3 = (float)(H3 > W3 ? H3 : W3) / 4.0f;
     hipLaunchKernelGGL((al_offset_conv_h_kernel<32>), g3, dim3(256), 0, s, g->p3cl, g->off, H3, W3, g->b3c1of, g->b3c1.ob, mo3, g->ctrl, fs);
-    hipLaunchKernelGGL((al_dcn_h_kernel<32, 64, 0, AL_DCN3_CS>), dim3(AL_DCN3_CS * sslam::cdiv(W3, 32), H3, uF), dim3(256), 0, s, g->p3cl, g->off, nullptr, H3, W3, g->b3c1f, g->b3c1.b, nullptr, g->t3, g->t3cl, g->ctrl, fs);
+    hipLaunchKernelGGL((al_dcn_h_kernel<32, 64, 0, DCN3_CS>), dim3(DCN3_CS * sslam::cdiv(W3, 32), H3, uF), dim3(256), 0, s, g->p3cl, g->off, nullptr, H3, W3, g->b3c1f, g->b3c1.b, nullptr, g->t3, g->t3cl, g->ctrl, fs);
     hipLaunchKernelGGL((al_offset_conv_h_kernel<64>), g3, dim3(256), 0, s, g->t3cl, g->off, H3, W3, g->b3c2of, g->b3c2.ob, mo3, g->ctrl, fs);
-    hipLaunchKernelGGL((al_dcn_h_kernel<64, 64, 32, AL_DCN3_CS>), dim3(AL_DCN3_CS * sslam::cdiv(W3, 32), H3, uF), dim3(256), 0, s, g->t3cl, g->off, g->p3cl, H3, W3, g->b3c2f, g->b3c2.b, g->b3db, g->x3, nullptr, g->ctrl, fs);
+    hipLaunchKernelGGL((al_dcn_h_kernel<64, 64, 32, DCN3_CS>), dim3(DCN3_CS * sslam::cdiv(W3, 32), H3, uF), dim3(256), 0, s, g->t3cl, g->off, g->p3cl, H3, W3, g->b3c2f, g->b3c2.b, g->b3db, g->x3, nullptr, g->ctrl, fs);
     // block4 at 1/32
     const int H4 = Hp / 32, W4 = Wp / 32, HW4 = H4 * W4;
     const dim3 g4(sslam::cdiv(W4, 32), H4, uF);
@@ -2278,10 +2134,10 @@ int al_enqueue(sslam_aliked* g, int F, const FrameIn& srcs, int H, int W, int C,
     hipLaunchKernelGGL(al_avgpool_kernel, dim3(sslam::cdiv(64 * HW4, 256), uF), dim3(256), 0, s, g->x3, g->p4, 64, H3, W3, 4, fs, g->p4cl);
     const float mo4 = (float)(H4 > W4 ? H4 : W4) / 4.0f;
     hipLaunchKernelGGL((al_offset_conv_h_kernel<64>), g4, dim3(256), 0, s, g->p4cl, g->off, H4, W4, g->b4c1of, g->b4c1.ob, mo4, g->ctrl, fs);
-    const dim3 g4s(AL_DCN4_CS * sslam::cdiv(W4, 32), H4, uF);  // AL_DCN4_CS workgroups per tile, 128 / AL_DCN4_CS output channels each
-    hipLaunchKernelGGL((al_dcn_h_kernel<64, 128, 0, AL_DCN4_CS>), g4s, dim3(256), 0, s, g->p4cl, g->off, nullptr, H4, W4, g->b4c1f, g->b4c1.b, nullptr, g->t4, g->t4cl, g->ctrl, fs);
+    const dim3 g4s(DCN4_CS * sslam::cdiv(W4, 32), H4, uF);  // DCN4_CS workgroups per tile, 128 / DCN4_CS output channels each
+    hipLaunchKernelGGL((al_dcn_h_kernel<64, 128, 0, DCN4_CS>), g4s, dim3(256), 0, s, g->p4cl, g->off, nullptr, H4, W4, g->b4c1f, g->b4c1.b, nullptr, g->t4, g->t4cl, g->ctrl, fs);
     hipLaunchKernelGGL((al_offset_conv_h_kernel<128>), g4, dim3(256), 0, s, g->t4cl, g->off, H4, W4, g->b4c2of, g->b4c2.ob, mo4, g->ctrl, fs);
-    hipLaunchKernelGGL((al_dcn_h_kernel<128, 128, 64, AL_DCN4_CS>), g4s, dim3(256), 0, s, g->t4cl, g->off, g->p4cl, H4, W4, g->b4c2f, g->b4c2.b, g->b4db, g->x4, nullptr, g->ctrl, fs);
+    hipLaunchKernelGGL((al_dcn_h_kernel<128, 128, 64, DCN4_CS>), g4s, dim3(256), 0, s, g->t4cl, g->off, g->p4cl, H4, W4, g->b4c2f, g->b4c2.b, g->b4db, g->x4, nullptr, g->ctrl, fs);
     // gates
     hipLaunchKernelGGL(al_gate_kernel<32>, dim3(sslam::cdiv(H2 * W2, 256), uF), dim3(256), 0, s, g->x2, g->g2, H2 * W2, g->gw2, g->g2cl, fs);
     {
@@ -2610,13 +2466,6 @@ int sslam_aliked_debug_read(sslam_aliked* g, int which, void* dst, size_t bytes)
         case 16: src = g->pre3; cap = AGG_PRE * HWp / 64 * 4; break;
         case 17: src = g->pre4; cap = AGG_PRE * HWp / 1024 * 4; break;
         case 18: src = g->s8; cap = 8 * HWp * 4; break;
-#if defined(AL_AGG_LOAD_NOP) && AL_AGG_LOAD_NOP == 3
-        case 99: {                                                      // experiment: the packed-versus-scalar discrepancy record
-            SSLAM_REQUIRE(bytes <= sizeof(unsigned) * 64, "sslam_aliked_debug_read: 256 bytes");
-            SSLAM_HIP_CHECK(hipMemcpyFromSymbol(dst, HIP_SYMBOL(al_dbg_words), bytes));
-            return 0;
-        }
-#endif
         default: SSLAM_REQUIRE(false, "sslam_aliked_debug_read: unknown buffer %d", which);
     }
     SSLAM_REQUIRE(bytes <= cap, "sslam_aliked_debug_read: %zu bytes requested, buffer has %zu", bytes, cap);

@@ -95,25 +95,13 @@ struct FfnFusedArgs {
 #else
 #define FFN_STAMP_AT(i_)
 #endif
-#ifndef FFN_ABL
-#define FFN_ABL 0       // ubench ablations: 1 no MFMA, 2 no weight loads after the first steps, 4 no LN/GELU arithmetic, 8 no stores
-#endif
-#ifndef FFN_D1
-#define FFN_D1 4        // W1 fragment sets in flight per wave (steps of 4 KB)
-#endif
-#ifndef FFN_D2
-#define FFN_D2 8        // W2 fragment sets in flight per wave (steps of 2 KB)
-#endif
+constexpr int FFN_DEPTH1 = 4;       // W1 fragment sets in flight per wave (steps of 4 KB)
+constexpr int FFN_DEPTH2 = 8;       // W2 fragment sets in flight per wave (steps of 2 KB)
 // Ring depths of the 32-token tile (TT = 1: one or two pairs, pruned sets).  r05 measured twice the depth there (8 / 16 sets:
 // the tile's accumulators and LayerNorm values need 96 registers less, so it fits - 255 VGPRs, no spill - and the results are
 // bit-identical): 25.6 against 24.3 us per launch for one pair, 32.8 against 31.4 for two.  The 32-token tile does not wait
 // for its weights; what it cannot hide is the prologue / LayerNorm-GELU / epilogue chain that runs without an MFMA beside it.
-#ifndef FFN_D1_SMALL
-#define FFN_D1_SMALL FFN_D1
-#endif
-#ifndef FFN_D2_SMALL
-#define FFN_D2_SMALL FFN_D2
-#endif
+constexpr int FFN_DEPTH1_SMALL = FFN_DEPTH1, FFN_DEPTH2_SMALL = FFN_DEPTH2;
 
 __device__ __forceinline__ auto ffn_rsrc(const void* base, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
@@ -166,14 +154,11 @@ __device__ __forceinline__ float ffn_erf(float x) {        // Abramowitz & Stegu
 // moment) sat in front of the MFMAs.  Now a wave waits for exactly its own pieces of the next chunk with a counted
 // s_waitcnt - ffn_ops_after_chunk() replays the wave's issue order at compile time - and one barrier per chunk makes
 // the other waves' pieces visible.
-#ifndef FFN_LEADC_N
-#define FFN_LEADC_N 2
-#endif
-constexpr int FFN_LEADC = FFN_LEADC_N;
+constexpr int FFN_LEADC = 2;
 // vector-memory operations a wave issues after the last piece of chunk c and before the point where chunk c must be
 // in place (before the loop for chunk 0, else the start of step 4 c - 1: the fragment read runs one step ahead).
-// Program order: prologue = W1 set 0 (4 loads), chunk 0 (two pieces), W1 sets 1 .. FFN_D1 - 1, chunks 1 .. LEADC - 1 -
-// what step 0 needs first in the queue; step s = [wait point] MFMAs, W1 refill (4 loads, while s + FFN_D1 < 32), then
+// Program order: prologue = W1 set 0 (4 loads), chunk 0 (two pieces), W1 sets 1 .. FFN_DEPTH1 - 1, chunks 1 .. LEADC - 1 -
+// what step 0 needs first in the queue; step s = [wait point] MFMAs, W1 refill (4 loads, while s + FFN_DEPTH1 < 32), then
 // chunk s / 4 + LEADC when s % 4 == 0.
 constexpr int ffn_ops_after_chunk(int c, int d1, int nch = 8) {     // nch: chunks that arrive by LDS-DMA (FOLD: the x half only)
     int n = 0; bool seen = false;
@@ -191,12 +176,8 @@ constexpr int ffn_ops_after_chunk(int c, int d1, int nch = 8) {     // nch: chun
     return n;
 }
 template <int N> __device__ __forceinline__ void ffn_wait_vm() {
-#if FFN_ABL & 2
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (ablation builds skip vector-memory operations the count assumes)
-#else
     static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
-#endif
 }
 template <class F, int... I> __device__ __forceinline__ void ffn_static_for(F&& f, std::integer_sequence<int, I...>) {
     (f(std::integral_constant<int, I>{}), ...);
@@ -211,7 +192,7 @@ template <class F, int... I> __device__ __forceinline__ void ffn_static_for(F&& 
 // FOLD (TT = 1 only): the message half of the operand tile does not come from `msgs` - the tile merges the key-range
 // partials of its 32 tokens itself (lg_attn_merge_h_kernel's arithmetic, expression for expression) and writes the planes
 // straight into the LDS image: one launch and one HBM round trip of the context planes less per block of a single pair.
-template <int TT = 2, bool FOLD = false, int D1 = (TT == 1 ? FFN_D1_SMALL : FFN_D1), int D2 = (TT == 1 ? FFN_D2_SMALL : FFN_D2)>
+template <int TT = 2, bool FOLD = false, int D1 = (TT == 1 ? FFN_DEPTH1_SMALL : FFN_DEPTH1), int D2 = (TT == 1 ? FFN_DEPTH2_SMALL : FFN_DEPTH2)>
 __device__ __forceinline__ void ffn_fused_tile(const FfnFusedArgs& p, int grow0, int grow_cap, int n_valid,
                                                int* range_flag, _Float16* smem) {
     static_assert(TT == 1 || TT == 2, "one or two 32-token tiles per workgroup");
@@ -244,17 +225,11 @@ __device__ __forceinline__ void ffn_fused_tile(const FfnFusedArgs& p, int grow0,
     const auto r_w1 = ffn_rsrc(p.w1f, 2 * FFN_H * FFN_H * 2), r_w2 = ffn_rsrc(p.w2f, 2 * FFN_D * FFN_H * 2);
     // W1 fragment set of step ks: [hi jt0, hi jt1, lo jt0, lo jt1], 1 KiB each, 4 KiB per (step, wave)
     auto load_w1 = [&](int ks, half8 (&dst)[4]) {
-#if FFN_ABL & 2
-        if (ks >= D1) return;
-#endif
         const int base = (ks * 8 + wave) * 4096;
 #pragma unroll
         for (int f = 0; f < 4; ++f) dst[f] = ffn_ldfrag(r_w1, lane16, base + f * 1024);
     };
     auto load_w2 = [&](int ks, half8 (&dst)[2]) {
-#if FFN_ABL & 2
-        if (ks >= D2) return;
-#endif
         const int base = (ks * 8 + wave) * 2048;
         dst[0] = ffn_ldfrag(r_w2, lane16, base);
         dst[1] = ffn_ldfrag(r_w2, lane16, base + 1024);
@@ -376,14 +351,9 @@ __device__ __forceinline__ void ffn_fused_tile(const FfnFusedArgs& p, int grow0,
         for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
             for (int tt = 0; tt < TT; ++tt) {
-#if FFN_ABL & 1
-                c1[jt][tt][0] += (float)w[jt][0] + (float)ah[tt][1];
-                c2[jt][tt][0] += (float)w[2 + jt][0] + (float)al[tt][1];
-#else
                 c1[jt][tt] = mfma16(w[jt], ah[tt], c1[jt][tt]);
                 c2[jt][tt] = mfma16(w[jt], al[tt], c2[jt][tt]);
                 c2[jt][tt] = mfma16(w[2 + jt], ah[tt], c2[jt][tt]);
-#endif
             }
     };
     {
@@ -499,11 +469,7 @@ __device__ __forceinline__ void ffn_fused_tile(const FfnFusedArgs& p, int grow0,
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float y = v[jt][tt][8 * s + e] * gmm[e] + btt[e];
-#if FFN_ABL & 4
-                    ge[e] = y;
-#else
                     ge[e] = 0.5f * y * (1.0f + ffn_erf(y * 0.70710678118654752440f));
-#endif
                 }
                 uint4 hi, lo;
                 split8_fast(ge, hi, lo, amax);
@@ -533,14 +499,9 @@ __device__ __forceinline__ void ffn_fused_tile(const FfnFusedArgs& p, int grow0,
     auto mma2 = [&](const half8 (&w)[2], const half8 (&gh)[TT], const half8 (&gl)[TT]) {
 #pragma unroll
         for (int tt = 0; tt < TT; ++tt) {
-#if FFN_ABL & 1
-            d1[tt][0] += (float)w[0][0] + (float)gh[tt][1];
-            d2[tt][0] += (float)w[1][0] + (float)gl[tt][1];
-#else
             d1[tt] = mfma16(w[0], gh[tt], d1[tt]);
             d2[tt] = mfma16(w[0], gl[tt], d2[tt]);
             d2[tt] = mfma16(w[1], gh[tt], d2[tt]);
-#endif
         }
     };
     {
@@ -611,7 +572,6 @@ __device__ __forceinline__ void ffn_fused_tile(const FfnFusedArgs& p, int grow0,
         float o[8] = {(ya.x + ba.x) + xa[it].x, (ya.y + ba.y) + xa[it].y, (ya.z + ba.z) + xa[it].z, (ya.w + ba.w) + xa[it].w,
                       (yb.x + bb.x) + xb[it].x, (yb.y + bb.y) + xb[it].y, (yb.z + bb.z) + xb[it].z, (yb.w + bb.w) + xb[it].w};
         float* xr = p.x + (size_t)(grow0 + tok) * FFN_D + col;
-#if !(FFN_ABL & 8)
         *reinterpret_cast<float4*>(xr) = make_float4(o[0], o[1], o[2], o[3]);
         *reinterpret_cast<float4*>(xr + 4) = make_float4(o[4], o[5], o[6], o[7]);
         uint4 hi, lo;
@@ -638,9 +598,6 @@ __device__ __forceinline__ void ffn_fused_tile(const FfnFusedArgs& p, int grow0,
                 }
             }
         }
-#else
-        if (o[0] == 123.456f) *xr = o[1];
-#endif
     }
     split_range_check(amax, range_flag);
     if (with_conf && p.unconf) {

@@ -202,10 +202,7 @@ __device__ __forceinline__ void gemm_mainloop_h(const GemmAH& ga, SplitPtr W, in
 // the other half one tile later - every line crossed L2 -> L1 twice, and the per-CU LDS-DMA intake,
 // which bounds these loops, carried 50 % useful bytes.)  The 64-deep ring GEMM of the single-pair
 // path reads two adjacent panels per k-tile (2 x 512 B runs per DMA instruction).
-#ifndef SSLAM_PANEL_K
-#define SSLAM_PANEL_K 32
-#endif
-constexpr int PANEL_K = SSLAM_PANEL_K;
+constexpr int PANEL_K = 32;
 static_assert(PANEL_K == 32 || PANEL_K == 64, "k-panel width");
 __host__ __device__ __forceinline__ size_t panel_index(int row, int col, int rows_total) {
     return ((size_t)(col / PANEL_K) * rows_total + row) * PANEL_K + (col % PANEL_K);
@@ -334,7 +331,6 @@ __device__ __forceinline__ void gemm_mainloop_ring(const GemmAH& ga, SplitPtr W,
                 fwh[j] = *reinterpret_cast<const half8*>(swh + o);
                 fwl[j] = *reinterpret_cast<const half8*>(swl + o);
             }
-#if !defined(SSLAM_DBG_NOMFMA)
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -343,9 +339,6 @@ __device__ __forceinline__ void gemm_mainloop_ring(const GemmAH& ga, SplitPtr W,
                     acc2[i][j] = mfma16(fah[i], fwl[j], acc2[i][j]);
                     acc2[i][j] = mfma16(fal[i], fwh[j], acc2[i][j]);
                 }
-#else
-            acc1[0][0][0] += (float)fah[0][0] + (float)fal[0][1] + (float)fwh[0][2] + (float)fwl[0][3];
-#endif
         }
     }
 }

@@ -1152,9 +1152,6 @@ __device__ __forceinline__ void linear_h_epilogue(const LinearArgsH& p, const Ro
     constexpr int ITERS = BM * CH / NT;
     const int grow0 = (int)ibase + rd.row0;            // global plane row of tile row 0
     float4 pre_a[(EPI == EPH_QKV || EPI == EPH_RESID) ? ITERS : 1], pre_b[(EPI == EPH_QKV || EPI == EPH_RESID) ? ITERS : 1];
-#ifndef LG_EPI_PREFETCH
-#define LG_EPI_PREFETCH 1      // A/B switch (scripts/ab_lib.sh): 0 = load inside the unit loop
-#endif
     auto pre_load = [&](int it) {
         const int u = t + it * NT, rl = u / CH, cl = (u % CH) * 8;
         if constexpr (EPI == EPH_QKV) {
@@ -1167,7 +1164,7 @@ __device__ __forceinline__ void linear_h_epilogue(const LinearArgsH& p, const Ro
             pre_b[it] = *reinterpret_cast<const float4*>(p.out + o + 4);
         }
     };
-    if constexpr (LG_EPI_PREFETCH && (EPI == EPH_QKV || EPI == EPH_RESID)) {
+    if constexpr (EPI == EPH_QKV || EPI == EPH_RESID) {
         if (!v_tile) {
 #pragma unroll
             for (int it = 0; it < ITERS; ++it) pre_load(it);
@@ -1188,20 +1185,9 @@ __device__ __forceinline__ void linear_h_epilogue(const LinearArgsH& p, const Ro
         }
     __syncthreads();
 
-#ifndef LG_EPI_FAST_SPLIT
-#define LG_EPI_FAST_SPLIT 1    // A/B switch (scripts/ab_lib.sh): 0 = the branchy scalar split_f32 per value
-#endif
     float amax = 0.0f;
     auto split8 = [&](const float (&v)[8], uint4& hi, uint4& lo) {
-#if LG_EPI_FAST_SPLIT
         sslam::split8_fast(v, hi, lo, amax);
-#else
-        half8 hh, ll;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { _Float16 a, b2; split_f32(v[e], a, b2, range_flag_of(p.ctrl, rd.img)); hh[e] = a; ll[e] = b2; }
-        hi = *reinterpret_cast<uint4*>(&hh);
-        lo = *reinterpret_cast<uint4*>(&ll);
-#endif
     };
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
@@ -1210,7 +1196,6 @@ __device__ __forceinline__ void linear_h_epilogue(const LinearArgsH& p, const Ro
         const int rl = u / CH, cl = (u % CH) * 8;
         const int row = rd.row0 + rl, col = col0 + cl;
         if (row >= rd.n) continue;
-        if constexpr (!LG_EPI_PREFETCH && (EPI == EPH_QKV || EPI == EPH_RESID)) pre_load(it);
         float v[8];
         {
             const float4 a = *reinterpret_cast<const float4*>(&epi[rl * ELD + cl]);
@@ -1317,9 +1302,6 @@ __global__ __launch_bounds__(512) void lg_linear_h_kernel(LinearArgsH p) {
     gemm_mainloop_ring<BM, BN, TM, TN, ring_depth<BM, BN>()>(ga, p.W, p.NIc * p.Kc, p.K, (int)ibase + rd.row0,
                                                              (int)ibase + p.Kc, col0, p.N, lg_ring, c1, c2);
     if (threadIdx.x >= 256) return;                    // producer waves (4-7) are done
-#if defined(SSLAM_DBG_NOEPI)
-    if (c1[0][0][0] != 123456.0f) return;
-#endif
     linear_h_epilogue<BM, BN, TM, TN, 2, 256, EPI>(p, rd, col0, ibase, c1, c2, lg_ring);
 }
 
@@ -1344,9 +1326,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void lg_linear_big_kernel(LinearAr
     constexpr int NW = WM * WN;
     sslam::gemm_mainloop_big<BM, BN, WM, WN>(ga, p.W, p.NIc * p.Kc, p.K, (int)ibase + rd.row0, (int)ibase + p.Kc, col0,
                                              p.N, lg_ring, c1, c2);
-#if defined(SSLAM_DBG_NOEPI)
-    if (c1[0][0][0] != 123456.0f) return;
-#endif
     linear_h_epilogue<BM, BN, TM, TN, WN, NW * 64, EPI>(p, rd, col0, ibase, c1, c2, lg_ring);
 }
 

@@ -1,4 +1,6 @@
 # A/B of the XCD-aware tile placement of ALIKED's halo kernels: per-kernel time and HBM-side traffic, placement on / off.
+# RECORD of a decided A/B (profiles/README.md, r06_pmc_traffic_aliked): needs the tree of commit c4c4676 (the last one whose kernel sources had build switches);
+# on later sources the flag it passes selects nothing and all three builds are the product.
 export SSLAM_EXPERIMENT_BUILD=1
 cd $GRAFT_REPO_ROOT
 for B in ${BANDS:-0 1 2}; do

@@ -16,7 +16,8 @@ usage: agg_isa_patch.py IN.s OUT.s MODE
   probe:REG:K         v88 = REG in front of the K-th packed instruction, stored where 1 / ||F|| was (see apply())
   MODE+MODE           several of the above
   list                print the packed instructions with their ordinals and whether a source is a load destination; no output file
-IN.s: `hipcc --offload-arch=gfx950 -O3 -std=c++17 -DAL_AGG_FAST_SELU=2 -DAL_AGG_PACKED=1 --cuda-device-only -S scripts/ubench/agg_victim.hip`."""
+IN.s: the assembly scripts/agg_isa_variants.sh writes (`hipcc ... --cuda-device-only -S scripts/ubench/agg_victim.hip` with the two
+build switches of the failing shape; the kernel source had them up to commit c4c4676)."""
 import re, sys
 
 KERNEL = "_ZN12_GLOBAL__N_119al_aggregate_kernelENS_3PyrEPKfPfS3_m"

@@ -1,3 +1,5 @@
+# RECORD (profiles/r06_aggregate_rnorm_diagnosis.md): needs the tree of commit c4c4676 (the last one whose kernel sources had build switches); on later sources the
+# flags it passes select nothing and all three builds are the product.
 # r06, VERDICT r05 item 8: the one-kernel bisect.  ONLY al_aggregate_kernel changes between the builds (the rest of the library
 # is bit for bit the same code): the hardware exponential in its tail (AL_AGG_FAST_SELU=2, the switch that made r04 / r05's builds
 # fail) with packed-fp32 instructions allowed in it (AL_AGG_PACKED=1: the SLP vectoriser's v_pk_mul_f32 / v_pk_fma_f32 shape) or

@@ -1,6 +1,6 @@
 """WHAT are the wrong 1 / ||F|| values of al_aggregate_kernel's unstable code shapes?
 
-Run on a library built with a failing variant (scripts/diag_agg_rnorm.sh: -DAL_AGG_FAST_SELU=2).  The concurrency stress of
+Run on a library built with a failing variant (scripts/diag_agg_rnorm.sh; the kernel source had that switch up to commit c4c4676).  The concurrency stress of
 scripts/stress_aliked_repeat.py (3 extractor instances x 2 frames x 4 un-synchronised calls per repeat); for every repeat in
 which frame 0's `rnorm` map of an instance differs from the first run, for each run of differing pixels:
 

@@ -4,9 +4,8 @@
 // fault of this repository (1 / ||F|| missing one gather's term in lanes 48..63, only in the packed-fp32 code shape, only with
 // other queues' kernels on the GPU).  This file asks the next question: is the kernel BY ITSELF, with nothing of the extractor
 // around it, enough of a victim?  It includes the product's source as it lies (no copy), so the kernel is the very code the
-// library ships, compiled with whatever -DAL_AGG_* the build line gives (scripts/agg_victim.sh):
-//     -DAL_AGG_FAST_SELU=2 -DAL_AGG_PACKED=1      the failing shape (147 v_pk_*)
-//     (nothing)                                     the product's shape (packed fp32 off)
+// library ships.  The failing shape (147 v_pk_*) that scripts/agg_victim.sh builds beside the product's (packed fp32 off) was
+// selected by two build switches of the kernel source: that library needs the tree of commit c4c4676, the last one that had them.
 // C entry points (ctypes, scripts/agg_victim_run.py): victim_create / victim_run / victim_poll / victim_destroy.
 #include "../../opencv-simpleslam_amd/csrc/aliked_kernels.hip"
 

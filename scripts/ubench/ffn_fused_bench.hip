@@ -1,6 +1,8 @@
 // micro-benchmark + correctness check of the fused FFN tile (csrc/ffn_fused.hpp) on the batched LightGlue shape
 // (M = 32768 token rows = 8 pairs x 2 images x 2048), against an fp64 host evaluation of sampled rows.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I opencv-simpleslam_amd/csrc scripts/ubench/ffn_fused_bench.hip -o /tmp/ffn_fused && /tmp/ffn_fused
+// (the ablation runs of ffn_fused_abl.sh / ffn_fused_sched.sh behind profiles/r03_ffn_fused_*.log need the tree of commit c4c4676:
+//  the kernel has no ablation arms any more, this file times and checks the one form there is)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -133,7 +135,7 @@ int main(int argc, char** argv) {
         CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         const double us = ms * 1e3 / reps, gf = 2.0 * M * (512.0 * 512 + 256.0 * 512) / 1e9;
-        printf("  fused FFN (ABL %d): %7.1f us / launch   %6.1f TFLOP/s algorithmic (%.1f %% of the f16 peak executed x3)\n", FFN_ABL, us,
+        printf("  fused FFN: %7.1f us / launch   %6.1f TFLOP/s algorithmic (%.1f %% of the f16 peak executed x3)\n", us,
                gf / us * 1e3 /* GFLOP / us = 1e3 TFLOP/s */, 3 * gf / us * 1e3 / 2500.0 * 100.0);
         CK(hipMemcpy(d_x, x.data(), x.size() * 4, hipMemcpyHostToDevice));
     }

@@ -1,4 +1,6 @@
 # fused FFN ubench: scheduling variants x ablations (run on the GPU box)
+# RECORD (profiles/README.md, r03_ffn_fused_*.log): needs the tree of commit c4c4676 (the last one whose kernel sources had build switches);
+# on later sources the flags it passes select nothing.
 cd $GRAFT_REPO_ROOT
 for sch in ${SCHEDS:-0 1 2}; do
 for abl in ${ABLS:-0 1}; do
