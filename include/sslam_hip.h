@@ -224,6 +224,41 @@ int sslam_triangulate_2view_dev(sslam_ctx* ctx, int n_max, const int32_t* n_dev,
                                 double reproj_px_max, double* X_out_dev, int32_t* ij_out_dev,
                                 int32_t* info_out_dev, int32_t* reason_out_dev, double* diag_out_dev);
 
+/* ------------------------------------------------ two-view relative pose
+ * Replaces `cv2.recoverPose(E, pts_ref, pts_cur, K)` in `recover_pose_from_fundamental`
+ * (slam/core/two_view_bootstrap.py:207-208) and in the tracking-lost fallback (slam/monocular/main_revamped.py:514):
+ * OpenCV 4.x's five-point.cpp restated.  Pixels are widened to double and normalised (x - cx) / fx, (y - cy) / fy;
+ * `decomposeEssentialMat` (3 x 3 one-sided Jacobi SVD, U = -U / Vt = -Vt where a determinant is negative,
+ * R1 = U W Vt, R2 = U W^T Vt, t = U[:,2]); the candidates [R1|t] [R2|t] [R1|-t] [R2|-t] against [I|0]; every
+ * match triangulated by the DLT of `cv2.triangulatePoints` into Q and judged per candidate:
+ * Q2 Q3 > 0, then Q /= Q3 and Q2 < distance_thresh, then Q = P Q and 0 < Q2 < distance_thresh (a zero Q3 gives
+ * inf / NaN and every comparison with those is false).  The winner by OpenCV's own >= chain, candidate 1 first.
+ * fp64 throughout.  Parity with cv2 itself is unpinned (tests/relative_pose_ref.py names what could not be confirmed).
+ *   pts1, pts2 : float32 [n][2] matched pixels (host);  n == 0 is legal: all counts zero, candidate 1 wins
+ *   E9, K9 row-major 3x3 (fx, fy, cx, cy are read);  distance_thresh : cv2's default is 50
+ *   mask_in[n] (may be NULL) : each candidate's mask is mask_in & (good ? 255 : 0) bytewise - a 0/1 mask stays 0/1;
+ *   without it the mask is 255 / 0
+ *   R_out9, t_out3, mask_out[n] : the winner's R, its +-t and its mask
+ *   info_out[8] : good (the winner's non-zero count), n, winner 0..3, good1, good2, good3, good4, 0 */
+int sslam_recover_pose_host(sslam_ctx* ctx, int n, const float* pts1, const float* pts2, const double* E9,
+                            const double* K9, double distance_thresh, const unsigned char* mask_in,
+                            double* R_out9, double* t_out3, unsigned char* mask_out, int32_t* info_out);
+
+/* `triangulation_metrics` (slam/core/two_view_bootstrap.py:127-156) and `_triangulate_points_cv` (:314-326):
+ * `cv2.undistortPoints` without distortion ((x - cx) * (1 / fx) in double, rounded to float32 as OpenCV 4.x does for
+ * float32 input), the DLT against [I|0] and [R|t], X = Xh[:3] / (Xh[3] + 1e-12), z1 = X[2], z2 = (R X + t)[2],
+ * cos = v1.v2 / (|v1||v2| + 1e-12) with v1 = X, v2 = X + R^T t, clipped to [-1, 1].
+ *   sel[n] (may be NULL: every match) : the matches with a non-zero byte take part, compacted in match order
+ *   (how the reference passes pts[inl]); N = their number, at most 16384 (more is an error)
+ *   K9, R9 row-major 3x3, t3
+ *   metrics_out[2] : count(z1 > 0 and z2 > 0) / N, degrees(median(arccos(cos))) - for an even N the mean of the
+ *   two middle values, exact;  info_out[4] : N, the count in front, 0, 0.  N < 2 gives metrics 0, 0 and
+ *   info[0] = 0 (the reference's early return).  Behaviour on NaN inputs is unspecified.
+ *   X_out[N*3], z_out[N*2] (may be NULL) : the points and their two depths, in selected order */
+int sslam_two_view_metrics_host(sslam_ctx* ctx, int n, const float* pts1, const float* pts2,
+                                const unsigned char* sel, const double* K9, const double* R9, const double* t3,
+                                double* metrics_out, int32_t* info_out, double* X_out, double* z_out);
+
 /* ------------------------------------------- 2D-3D association for tracking
  * Replaces the per-point loop of `reproject_and_match_2d3d` (slam/core/pnp_utils.py:224-304) for
  * float descriptors: projection (`_project_points` :127-141), radius search (cKDTree :238, :265),

@@ -8,7 +8,8 @@
 //     per view), its null vector from a ONE-SIDED (Hestenes) Jacobi SVD of A itself, as OpenCV's JacobiSVD does - never
 //     from A^T A, whose condition number is the square (the low-parallax pairs are the ones the gates must judge);
 //   * the sweep cap (30, OpenCV's) and the rotation order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) are fixed and a match's
-//     arithmetic involves no other match, so a result does not depend on the launch shape;
+//     arithmetic involves no other match, so a result does not depend on the launch shape (dlt_svd.hpp, shared with
+//     relative_pose_kernels.hip);
 //   * one reason per match, decided in the reference's order: invalid_w, low_parallax, bad_depth, behind_cam, high_reproj,
 //     else kept (the reference's `continue`s).
 // PARITY UNPINNED: cv2 is absent here; tests/triangulate_ref.py restates the reference with LAPACK's SVD.
@@ -17,6 +18,7 @@
 // match, 4096 of them on one CU would take four turns of a full workgroup) and a one-workgroup tail that compacts the kept
 // matches in order (sslam::block_compact) and sums the reason counters.
 #include "common.hpp"
+#include "dlt_svd.hpp"
 #include "geom_common.hpp"
 
 #include <cfloat>
@@ -26,7 +28,6 @@ namespace {
 
 constexpr int TR_T = 256;            // threads per workgroup of the per-match launch
 constexpr int TR_TAIL_T = 1024;      // the compaction tail: one workgroup, 1024 matches per turn
-constexpr int TR_SWEEPS = 30;        // OpenCV's JacobiSVD iteration cap for a 4 x 4 matrix
 constexpr int TR_REASONS = 6;
 
 enum : int { TR_KEPT = 0, TR_INVALID_W = 1, TR_LOW_PARALLAX = 2, TR_BAD_DEPTH = 3, TR_BEHIND_CAM = 4, TR_HIGH_REPROJ = 5 };
@@ -47,34 +48,6 @@ struct TRArgs {
 };
 
 __device__ __forceinline__ int tr_n(const TRArgs& a) { return a.n_dev ? min(max(a.n_dev[0], 0), a.n) : a.n; }
-
-// One Jacobi rotation of columns I, J of A (stored column-major: A[col][row]) and of V; false when they are already orthogonal.
-template <int I, int J>
-__device__ __forceinline__ bool tr_rotate(double (&A)[4][4], double (&V)[4][4]) {
-    double a = 0, b = 0, p = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { a += A[I][k] * A[I][k]; b += A[J][k] * A[J][k]; p += A[I][k] * A[J][k]; }
-    if (fabs(p) <= (DBL_EPSILON * 10) * sqrt(a * b)) return false;
-    p *= 2;
-    const double beta = a - b, gamma = hypot(p, beta);
-    double c, s;
-    if (beta < 0) {
-        const double delta = (gamma - beta) * 0.5;
-        s = sqrt(delta / gamma);
-        c = p / (gamma * s * 2);
-    } else {
-        c = sqrt((gamma + beta) / (gamma * 2));
-        s = p / (gamma * c * 2);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double t0 = c * A[I][k] + s * A[J][k], t1 = c * A[J][k] - s * A[I][k];
-        A[I][k] = t0; A[J][k] = t1;
-        const double v0 = c * V[I][k] + s * V[J][k], v1 = c * V[J][k] - s * V[I][k];
-        V[I][k] = v0; V[J][k] = v1;
-    }
-    return true;
-}
 
 // P = K T[:3,:] (row-major 3 x 4)
 __device__ __forceinline__ void tr_projection(const double* K, const double* T, double* P) {
@@ -119,36 +92,8 @@ __global__ __launch_bounds__(TR_T) void tr_match_kernel(TRArgs a) {
         double P1[12], P2[12];
         tr_projection(a.K, a.T1, P1);
         tr_projection(a.K, a.T2, P2);
-        double A[4][4], V[4][4];                       // [column][row]
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            A[k][0] = u1 * P1[8 + k] - P1[k];
-            A[k][1] = v1 * P1[8 + k] - P1[4 + k];
-            A[k][2] = u2 * P2[8 + k] - P2[k];
-            A[k][3] = v2 * P2[8 + k] - P2[4 + k];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) V[k][r] = k == r ? 1.0 : 0.0;
-        }
-        for (int sweep = 0; sweep < TR_SWEEPS; ++sweep) {
-            bool changed = tr_rotate<0, 1>(A, V);
-            changed |= tr_rotate<0, 2>(A, V);
-            changed |= tr_rotate<0, 3>(A, V);
-            changed |= tr_rotate<1, 2>(A, V);
-            changed |= tr_rotate<1, 3>(A, V);
-            changed |= tr_rotate<2, 3>(A, V);
-            if (!changed) break;
-        }
-        // the column with the smallest norm (the first of equals) carries the null vector
-        double best = 0, X4[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const double s = A[k][0] * A[k][0] + A[k][1] * A[k][1] + A[k][2] * A[k][2] + A[k][3] * A[k][3];
-            if (k == 0 || s < best) {
-                best = s;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) X4[r] = V[k][r];
-            }
-        }
+        double X4[4];
+        sslam::dlt_null_vector(P1, P2, u1, v1, u2, v2, X4);
         const double w = X4[3];
         const bool valid_w = isfinite(w) && fabs(w) > 1e-12;
         double X[3] = {X4[0] / w, X4[1] / w, X4[2] / w};
