@@ -397,7 +397,9 @@ int sslam_lightglue_match_dev(sslam_lightglue* lg, const float* xy0, const float
  * Host arrays of n_pairs entries: xy0[p] / desc0[p] / xy1[p] / desc1[p] device pointers, M[p] / N[p]
  * row bounds, m_dev[p] / n_dev[p] device counts (the arrays or single entries may be NULL).
  * Outputs (device): pair p writes ij_out + p*out_stride*2, score_out + p*out_stride, info_out + 4p;
- * out_stride >= min(M[p], N[p]).  Each pair's result is the one sslam_lightglue_match_dev gives. */
+ * out_stride >= min(M[p], N[p]).  Each pair's result is the one sslam_lightglue_match_dev gives.
+ * Images of one call with equal source pointers (and bound) are recognised as one frame, whose part of the forward that
+ * depends on one image alone is then computed once; results are unchanged. */
 int sslam_lightglue_match_batch_dev(sslam_lightglue* lg, int n_pairs, const float* const* xy0,
                                     const float* const* desc0, const int32_t* const* m_dev, const int32_t* M,
                                     const float* const* xy1, const float* const* desc1,
@@ -431,6 +433,12 @@ int sslam_lightglue_debug_key_split(sslam_lightglue* lg, int ks);
  * (a token's FFN arithmetic is the same in both: bit-identical), 5 = batched form with the token heads (early stop /
  * pruning inputs) as a launch of their own instead of in the cross block's fused FFN. */
 int sslam_lightglue_debug_big_gemm(sslam_lightglue* lg, int mode);
+/* Shared frames of one enqueue (equal xy / desc / count pointers, bound and image size): 1 (default) = the prologue and the
+ * self block of layer 0 run once per distinct frame and a copy kernel hands the state to the other images that name it,
+ * 0 = every image is computed.  Bit-identical results; the fp32 path (precision 0) always computes every image.
+ * _share_info: out[0] = distinct images of the last enqueue, out[1] = 1 when its launch sequence holds that copy kernel. */
+int sslam_lightglue_debug_share_frames(sslam_lightglue* lg, int enable);
+int sslam_lightglue_debug_share_info(sslam_lightglue* lg, int32_t* out);
 /* Precision-study hook (profiles/r04_split_study.md; the product never sets it): drop cross terms of the three-term
  * split products and measure what that does to the matches.  mask: 0x01 / 0x02 K / Q as one fp16 plane in the logits,
  * 0x04 / 0x08 P / V as one plane in the context, 0x10 / 0x20 activation low plane dropped in the projections / the FFN,

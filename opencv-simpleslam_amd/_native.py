@@ -90,6 +90,8 @@ def _signatures():
         "sslam_lightglue_range_overflow": (i32, [vp, c_int_p]),
         "sslam_lightglue_debug_key_split": (i32, [vp, i32]),
         "sslam_lightglue_debug_big_gemm": (i32, [vp, i32]),
+        "sslam_lightglue_debug_share_frames": (i32, [vp, i32]),
+        "sslam_lightglue_debug_share_info": (i32, [vp, vp]),
         "sslam_lightglue_debug_split_form": (i32, [vp, i32]),
         "sslam_lightglue_set_conf": (i32, [vp, f32, f32, f32, i32]),
         "sslam_lightglue_match_host": (i32, [vp, vp, vp, i32, vp, vp, i32, f32, vp, vp, c_int_p, c_int_p]),

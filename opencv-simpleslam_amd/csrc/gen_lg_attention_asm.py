@@ -457,7 +457,7 @@ e(".Lzdone:")
 e(f"    s_lshr_b32 {S_IMG}, s58, 2")
 e(f"    s_and_b32 {S_HEAD}, s58, 3")
 e(f"    s_lshl_b32 {S_Q0}, s59, 7")
-# ctrl of the pair: 64 bytes each: n[2] at 0, stop at 24, range flag at 40
+# ctrl of the pair: 64 bytes each: n[2] at 0, stop at 24, the range flags of its two images at 40 and 44
 e(f"    s_lshr_b32 {S_TMP}, {S_IMG}, 1")
 e(f"    s_lshl_b32 {S_TMP}, {S_TMP}, 6")
 e(f"    s_add_u32 s20, s20, {S_TMP}")
@@ -737,13 +737,15 @@ for half in range(2):
         e(f"    global_store_dwordx2 {v(addr)}, {v(HI, 2)}, s[16:17] offset:{16 * g4}")
         e(f"    global_store_dwordx2 {v(addr)}, {v(LO, 2)}, s[18:19] offset:{16 * g4}")
         e("    s_nop 0")
-# a finite |value| >= 65520 left through an fp16 plane: raise the pair's range flag (split_range_check)
+# a finite |value| >= 65520 left through an fp16 plane: raise the image's range flag, the word of its side (split_range_check)
 e(f"    v_cmp_ge_f32_e64 {S_M0}, {v(AMAX)}, {S_C65520}")
 e(f"    v_cmp_lt_f32_e64 {S_M1}, {v(AMAX)}, {S_CINF}")
 e(f"    s_and_b64 {S_M0}, {S_M0}, {S_M1}")
 e(f"    s_and_b64 exec, exec, {S_M0}")
 e("    s_cbranch_execz .Lend")
-e(f"    v_mov_b32_e32 {v(T + 7)}, 0")
+e(f"    s_and_b32 {S_TMP}, {S_IMG}, 1")
+e(f"    s_lshl_b32 {S_TMP}, {S_TMP}, 2")
+e(f"    v_mov_b32_e32 {v(T + 7)}, {S_TMP}")                     # 4 (img & 1)
 e(f"    v_mov_b32_e32 {v(T + 8)}, 1")
 e(f"    global_store_dword {v(T + 7)}, {v(T + 8)}, s[20:21] offset:40")
 e(".Lend:")

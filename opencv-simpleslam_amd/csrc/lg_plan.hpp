@@ -25,6 +25,8 @@ struct LGHooks {
     int key_split = 0;           // debug_key_split: 0 by batch size; -5 .. 104, decoded in lg_plan
     int big_gemm = -1;           // debug_big_gemm: -1 by batch size; 0 .. 5, decoded in lg_plan
     int study = 0;               // debug_split_form: which cross terms of the split products are dropped (bit mask)
+    bool share_frames = true;    // debug_share_frames: a frame that several images of one enqueue name is computed once up to
+                                 // the end of layer 0's self block (lg_alias below)
 };
 
 enum class LGAttn { F32, FourWave, Asm };       // lg_attention_kernel | lg_attention_p_kernel | lg_attention_asm[_p1]_kernel
@@ -45,6 +47,9 @@ struct LGPlan {
                                  // one; otherwise lg_token_heads_kernel runs
     int layers;
     bool self_only_last;
+    bool share_frames;           // (s) images that lg_alias maps to an earlier one skip the prologue and layer 0's self block and
+                                 // receive the representative's state from lg_fanout_kernel.  The fp32 path (precision 0) keeps
+                                 // computing every image: it is the exact reference, not the product path
 };
 
 // NI = images of this enqueue (2 per pair); want_heads = the instance stops early or prunes (depth_conf > 0 || width_conf > 0)
@@ -54,6 +59,7 @@ inline LGPlan lg_plan(const LGHooks& h, int Kc, int NI, bool want_heads) {
     p.proj_split = p.split && !h.sim_exact;
     p.layers = h.layers;
     p.self_only_last = h.self_only;
+    p.share_frames = h.share_frames && p.split;
 
     // debug_key_split:   0 by size | -3 none | -5 by size, merge launch | 101 102 104 forced   -> the assembly kernel
     //                   -4 by size | -1 none |                          |   1   2   4 forced   -> the 4-wave r02 kernel
@@ -94,6 +100,28 @@ inline LGPlan lg_plan(const LGHooks& h, int Kc, int NI, bool want_heads) {
     if (p.ks == 1) p.merge = LGMerge::None;
     else p.merge = big && p.ffn_tile == LGFfnTile::T32 && h.study == 0 && fold_allowed ? LGMerge::InFfn : LGMerge::Launch;
     return p;
+}
+
+// Which images of one enqueue are the SAME frame.  Image j is an alias of the earliest image i < j whose source entries are
+// all equal - keypoint, descriptor and count pointers, the host bound and the 'image_size' pair - because everything before
+// the first cross block depends on those alone.  rep[j] = that earliest image (rep[j] == j: j is computed); an alias of an
+// alias therefore resolves to the earliest one.  Returns the number of distinct images.  The graph cache's key
+// (lg_enqueue_cached) holds every field compared here, so a cached graph always belongs to one alias structure.
+template <class PX, class PD, class PC>
+inline int lg_alias(int NI, const PX* xy, const PD* desc, const PC* cnt, const int* bound, const float* size_w,
+                    const float* size_h, int* rep) {
+    int distinct = 0;
+    for (int j = 0; j < NI; ++j) {
+        rep[j] = j;
+        for (int i = 0; i < j; ++i)
+            if (xy[i] == xy[j] && desc[i] == desc[j] && cnt[i] == cnt[j] && bound[i] == bound[j] && size_w[i] == size_w[j] &&
+                size_h[i] == size_h[j]) {
+                rep[j] = i;          // the first match is the earliest: i itself is never an alias of a later image
+                break;
+            }
+        distinct += rep[j] == j;
+    }
+    return distinct;
 }
 
 }  // namespace sslam

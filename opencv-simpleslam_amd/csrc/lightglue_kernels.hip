@@ -72,18 +72,22 @@ struct LGCtrl {
     int stop_layer;  // index i of the layer whose log_assignment is used
     int unconf;      // #tokens with confidence < threshold (both images)
     int n_matches;   // K (-1: the split-precision range flag below was raised, the result is invalid)
-    int range_overflow;  // a finite |value| >= 65520 reached an fp16 split while this pair was processed (gemm_f16x3.hpp)
-    int pad[5];
+    int range_side[2];   // a finite |value| >= 65520 reached an fp16 split while this image of the pair was processed
+                         // (gemm_f16x3.hpp; the assembly attention kernel stores at byte 40 + 4 side).  One word per SIDE, so
+                         // that a flag raised while a shared frame was computed once (lg_fanout_kernel) reaches exactly the
+                         // pairs that hold the frame; the pair is out of range when either word is set
+    int pad[4];
 };
+static_assert(sizeof(LGCtrl) == 64 && offsetof(LGCtrl, range_side) == 40, "gen_lg_attention_asm.py addresses the block by byte");
 constexpr int MAX_PAIRS = 16;    // batch capacity bound (kernel-argument tables are sized for it)
 
 __device__ __forceinline__ LGCtrl& ctrl_of(LGCtrl* c, int img) { return c[img >> 1]; }
 __device__ __forceinline__ const LGCtrl& ctrl_of(const LGCtrl* c, int img) { return c[img >> 1]; }
 __device__ __forceinline__ int n_of(const LGCtrl* c, int img) { return c[img >> 1].n[img & 1]; }
-// the range flag of the pair an image belongs to (the one word of the control block that kernels which
-// otherwise only read it may write)
+// the range flag of an image: its side's word in the pair's block (the one word of the control block that kernels
+// which otherwise only read it may write)
 __device__ __forceinline__ int* range_flag_of(const LGCtrl* c, int img) {
-    return &const_cast<LGCtrl*>(c)[img >> 1].range_overflow;
+    return &const_cast<LGCtrl*>(c)[img >> 1].range_side[img & 1];
 }
 
 // Per-image input sources of one call (host-built table passed by value): where the keypoints /
@@ -96,6 +100,12 @@ struct StageSrc {
     int bound[2 * MAX_PAIRS];
     float size_w[2 * MAX_PAIRS], size_h[2 * MAX_PAIRS];   // 'image_size' of the features (W, H); 0 = none: bounding box
 };
+// Which images of one enqueue are the same frame (lg_plan.hpp lg_alias), host-built and passed by value like StageSrc:
+// rep[i] = the earliest image with image i's sources (rep[i] == i: computed; otherwise an alias, filled by lg_fanout_kernel)
+struct AliasTab {
+    signed char rep[2 * MAX_PAIRS];
+    int distinct;                    // == NI: no image is shared, the forward runs as if the table did not exist
+};
 
 // ------------------------------------------------------------------------ //
 //  0. prepare: bbox-normalise keypoints, rotary tables, control block
@@ -104,15 +114,18 @@ struct StageSrc {
 __global__ __launch_bounds__(1024) void lg_prepare_kernel(
     StageSrc src, int Kc, float* __restrict__ in_xy /*[NI][Kc][2]*/, float* __restrict__ in_desc /*[NI][Kc][128]*/,
     float* __restrict__ bbox /*[NI][4]: shift x, shift y, scale, -*/, int* __restrict__ ind,
-    int* __restrict__ prune, LGCtrl* __restrict__ ctrl) {
+    int* __restrict__ prune, LGCtrl* __restrict__ ctrl, AliasTab al, LGCtrl* __restrict__ shadow) {
+    // `shadow` (only with shared frames): a second control array for the launches up to the end of layer 0's self block -
+    // the real one with n = 0 for alias images, whose blocks those kernels then leave as they leave any row block past the count
     const int img = blockIdx.x, side = img & 1;
+    const bool alias = al.rep[img] != img;
     const float* xy = src.xy[img];
     // device-resident counts (written by the extractor) are clamped to the host-side bound
     int n = src.bound[img], n_other = src.bound[img ^ 1];
     if (src.cnt[img]) n = min(max(src.cnt[img][0], 0), n);
     if (src.cnt[img ^ 1]) n_other = min(max(src.cnt[img ^ 1][0], 0), n_other);
     __shared__ float red[4][32];
-    {   // descriptors into the staging rows the input projection reads (16-byte pieces): 1 MB per image at 2048
+    if (!alias) {   // descriptors into the staging rows the input projection reads (16-byte pieces): 1 MB per image at 2048
         // keypoints - one workgroup moved it at a single CU's share of the memory system (28 of the kernel's 45 us), so the
         // copy is striped over gridDim.y workgroups; workgroup y = 0 does the rest of the preparation
         const float4* sd = reinterpret_cast<const float4*>(src.desc[img]);
@@ -156,7 +169,14 @@ __global__ __launch_bounds__(1024) void lg_prepare_kernel(
         bbox[img * 4 + 0] = sx / 2.0f; bbox[img * 4 + 1] = sy / 2.0f; bbox[img * 4 + 2] = fmaxf(sx, sy) / 2.0f;
         c.n[side] = n; c.n_prev[side] = n; c.n_orig[side] = n;
         if (side == 0) { c.stop = (n == 0 || n_other == 0) ? 2 : 0; c.stop_layer = NL - 1;
-                         c.unconf = 0; c.n_matches = 0; c.range_overflow = 0; }
+                         c.unconf = 0; c.n_matches = 0; c.range_side[0] = 0; c.range_side[1] = 0; }
+        if (shadow) {
+            // stop = 0 also where the pair is empty-sided: the frame may be live in another pair, and an empty image has n = 0
+            LGCtrl& h = ctrl_of(shadow, img);
+            h.n[side] = alias ? 0 : n; h.n_prev[side] = h.n[side]; h.n_orig[side] = n;
+            if (side == 0) { h.stop = 0; h.stop_layer = NL - 1; h.unconf = 0; h.n_matches = 0;
+                             h.range_side[0] = 0; h.range_side[1] = 0; }
+        }
     }
 }
 
@@ -1025,7 +1045,7 @@ __global__ __launch_bounds__(1024) void lg_emit_kernel(
         // a value left the fp16 range of the split-precision path while this pair was processed: its
         // matches are not fp32-grade - the count says so (-1) wherever the result travels, and the
         // instance remembers it (sslam_lightglue_range_overflow)
-        if (ctrl->range_overflow) { total = -1; *range_sticky = 1; }
+        if (ctrl->range_side[0] | ctrl->range_side[1]) { total = -1; *range_sticky = 1; }
         ctrl->n_matches = total;
         info_out[0] = total;
         info_out[1] = ctrl->stop_layer + 1;     // upstream "stop" = i + 1
@@ -1081,6 +1101,50 @@ __global__ __launch_bounds__(256) void lg_split_rows_kernel(const float* __restr
     }
 }
 constexpr int SPLIT_BLOCKS_PER_IMAGE = 64;
+
+// ---- shared frames (lg_plan.hpp lg_alias): the prologue and layer 0's self block ran on the representatives only, under the
+// shadow control array; here every alias image receives its representative's state - token rows, their split planes (k-panel
+// layout: one contiguous run of the image's rows per panel) and the rotary tables - as a pure copy of the rows below its count.
+// Nothing is recomputed or split again, so the alias holds the bits it would have computed itself.
+// RANGE FLAG.  A flag raised in the shared segment stands in the representative's side word of the SHADOW block.  Grid row
+// `img` ORs the word of its representative into its own side word of the real block - every image that holds the frame,
+// the representative included, and no other - unless its pair is empty-sided (stop = 2: nothing of that pair ran, or runs).
+struct FanoutArgs {
+    float* x; float* enc_cos; float* enc_sin; _Float16* xs_hi; _Float16* xs_lo;
+    int Kc; int rows_total;          // plane rows = NIc * Kc
+    LGCtrl* ctrl; const LGCtrl* shadow;
+    AliasTab al;
+};
+constexpr int FANOUT_BLOCKS_PER_IMAGE = 128;
+__global__ __launch_bounds__(256) void lg_fanout_kernel(FanoutArgs p) {
+    const int img = blockIdx.y, r = p.al.rep[img];
+    const LGCtrl& pc = ctrl_of(p.ctrl, img);
+    if (pc.stop) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && *range_flag_of(p.shadow, r)) *range_flag_of(p.ctrl, img) = 1;
+    if (r == img) return;
+    const unsigned n = (unsigned)pc.n[img & 1];                 // (== the representative's: same count pointer, same bound)
+    const unsigned t = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
+    // 16-byte units; `per` = units per token row
+    auto copy_rows = [&](void* base, size_t per) {
+        uint4* d = reinterpret_cast<uint4*>(base) + (size_t)img * p.Kc * per;
+        const uint4* s = reinterpret_cast<const uint4*>(base) + (size_t)r * p.Kc * per;
+        for (unsigned u = t; u < n * per; u += nt) d[u] = s[u];
+    };
+    copy_rows(p.x, D * 4 / 16);
+    copy_rows(p.enc_cos, ENC * 4 / 16);
+    copy_rows(p.enc_sin, ENC * 4 / 16);
+    constexpr unsigned PU = sslam::PANEL_K * 2 / 16;           // units per row of one panel
+    const unsigned run = n * PU;                                // one panel's run of this image
+    uint4* hi = reinterpret_cast<uint4*>(p.xs_hi);
+    uint4* lo = reinterpret_cast<uint4*>(p.xs_lo);
+    for (unsigned u = t; u < run * (D / sslam::PANEL_K); u += nt) {
+        const unsigned k = u / run, e = u - k * run;
+        const size_t po = (size_t)k * p.rows_total * PU + e;
+        const size_t di = po + (size_t)img * p.Kc * PU, si = po + (size_t)r * p.Kc * PU;
+        hi[di] = hi[si];
+        lo[di] = lo[si];
+    }
+}
 
 enum { EPH_QKV = 0, EPH_CROSS = 1, EPH_SPLIT = 2, EPH_F32 = 3, EPH_RESID = 4 };
 
@@ -1913,6 +1977,9 @@ struct sslam_lightglue {
     const float* tc_b[NL - 1];
     // workspace
     LGCtrl* ctrl;
+    LGCtrl* ctrl_shadow;             // shared frames: the control array of the launches up to layer 0's self block (lg_prepare_kernel)
+    int last_distinct = 0;           // distinct images of the last enqueue (lg_alias) and whether its launch sequence holds
+    bool last_fanout = false;        // lg_fanout_kernel: sslam_lightglue_debug_share_info
     int* range_sticky;               // device word: some pair of some call raised its range flag since the last read
     float *x, *enc_cos, *enc_sin, *q, *k, *v, *msg, *hid, *tx, *tc, *ts;
     float *o_part, *m_part, *l_part, *conf, *mat, *md, *sim, *rmax, *rlog, *cmax, *clog, *best0;
@@ -2073,11 +2140,11 @@ void launch_linear_h(hipStream_t s, int NI, const LinearArgsH& a) {
     hipLaunchKernelGGL((lg_linear_h_kernel<BM, BN, TM, TN, EPI>), grid, dim3(512), lds, s, a);   // 4 consumer + 4 producer waves
 }
 
-LinearArgsH linh(const sslam_lightglue* g, SplitPtr A0, SplitPtr A1, int lda, int K0, int K, const float* W,
+LinearArgsH linh(const sslam_lightglue* g, const LGCtrl* ctrl, SplitPtr A0, SplitPtr A1, int lda, int K0, int K, const float* W,
                  const float* b, int N) {
     LinearArgsH a{};
     a.A0 = A0; a.A1 = A1; a.lda = lda; a.K0 = K0; a.K = K;
-    a.W = wsp(g, W); a.bias = b; a.N = N; a.ctrl = g->ctrl; a.Kc = g->Kc; a.NIc = g->NIc;
+    a.W = wsp(g, W); a.bias = b; a.N = N; a.ctrl = ctrl; a.Kc = g->Kc; a.NIc = g->NIc;
     a.enc_cos = g->enc_cos; a.enc_sin = g->enc_sin; a.q_scale = 1.0f; a.k_scale = 1.0f;
     return a;
 }
@@ -2114,8 +2181,8 @@ int lg_load_attention_asm(int device) {
     return 0;
 }
 
-void launch_attention_h(sslam_lightglue* g, hipStream_t s, const LGPlan& plan, int NI, SplitPtr Q, SplitPtr K, SplitPtr VT,
-                        int cross) {
+void launch_attention_h(sslam_lightglue* g, hipStream_t s, const LGPlan& plan, int NI, const LGCtrl* ctrl, SplitPtr Q, SplitPtr K,
+                        SplitPtr VT, int cross) {
     const int KS = plan.ks, study = g->hooks.study;
     if (study) {          // precision study: a dropped cross term = its low-plane operand replaced by zeros (bit-identical to not issuing the MFMA)
         if (study & 0x01) K.lo = g->zero_plane;             // S = kh.qh + kh.ql          (K as one fp16 plane)
@@ -2123,14 +2190,14 @@ void launch_attention_h(sslam_lightglue* g, hipStream_t s, const LGPlan& plan, i
         if (study & 0x08) VT.lo = g->zero_plane;            // O = vh.ph + vh.pl          (V as one fp16 plane)
     }
     AttnArgsH a{Q, K, VT, cross, g->o_part, g->m_part, g->l_part, SplitOut{g->msgs_hi, g->msgs_lo}, KS, g->Kc,
-                g->NIc, g->ctrl, plan.p_single ? 1 : 0};     // O = vh.ph + vl.ph: study bit 0x04 (4-wave kernel only) or precision "f16x3p1"
+                g->NIc, ctrl, plan.p_single ? 1 : 0};     // O = vh.ph + vl.ph: study bit 0x04 (4-wave kernel only) or precision "f16x3p1"
     attn_event(g, s, true);
     if (plan.attn == LGAttn::Asm) {
         // the hand-scheduled assembly kernel - the arithmetic, LDS images and results of lg_attention_p_kernel (no key split: batched
         // launches, debug_key_split(lg, -3)) and of lg_attention_p_kernel's key ranges (single pairs) bit for bit, 8 - 10 % faster
         // (profiles/r03_attention_experiments.md)
         const int lks = KS == 4 ? 2 : KS == 2 ? 1 : 0;
-        AttnAsmArgs k{Q.hi, Q.lo, K.hi, K.lo, VT.hi, VT.lo, g->msgs_hi, g->msgs_lo, g->ctrl, cross, g->Kc, g->NIc,
+        AttnAsmArgs k{Q.hi, Q.lo, K.hi, K.lo, VT.hi, VT.lo, g->msgs_hi, g->msgs_lo, ctrl, cross, g->Kc, g->NIc,
                       sslam::cdiv(g->Kc, AQ), NI * NH * KS, 0u, NI * NH, lks, g->o_part, g->m_part, g->l_part};
         k.magic = k.nqb > 1 ? (unsigned)((1ull << 32) / (unsigned)k.nqb + 1) : 0u;
         size_t sz = sizeof(k);
@@ -2148,13 +2215,16 @@ void launch_attention_h(sslam_lightglue* g, hipStream_t s, const LGPlan& plan, i
     if (plan.merge != LGMerge::Launch) return;   // the kernel wrote the context planes itself / the fused FFN merges the partials
     const long n4 = (long)NI * NH * g->Kc * 16;
     hipLaunchKernelGGL(lg_attn_merge_h_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, g->o_part,
-                       g->m_part, g->l_part, SplitOut{g->msgs_hi, g->msgs_lo}, KS, g->Kc, NI, g->NIc, g->ctrl);
+                       g->m_part, g->l_part, SplitOut{g->msgs_hi, g->msgs_lo}, KS, g->Kc, NI, g->NIc, ctrl);
 }
 
 // one transformer layer (self + cross block) on the split-precision path
 // `heads`: the layer's cross-block FFN also evaluates the token heads on the new state (LGPlan::heads_in_ffn, not the last layer)
+// `shared` (layer 0 of an enqueue with shared frames, otherwise null): the self block runs under the shadow control array, i.e.
+// on the representatives only, and lg_fanout_kernel then hands their state to the aliases; the cross block sees all NI images
 void lg_layer_h(sslam_lightglue* g, hipStream_t s, const LGPlan& plan, int NI, const LGLayerW& l, int layer, bool self_only,
-                bool heads) {
+                bool heads, const AliasTab* shared) {
+    const LGCtrl* const self_ctrl = shared ? g->ctrl_shadow : g->ctrl;
     const SplitPtr xs{g->xs_hi, g->xs_lo}, msgs{g->msgs_hi, g->msgs_lo};
     const SplitPtr hids{g->hids_hi, g->hids_lo}, none{nullptr, nullptr};
     const SplitPtr qs{g->qs_hi, g->qs_lo}, ks{g->ks_hi, g->ks_lo}, vts{g->vts_hi, g->vts_lo};
@@ -2167,8 +2237,8 @@ void lg_layer_h(sslam_lightglue* g, hipStream_t s, const LGPlan& plan, int NI, c
     const float sm_scale = 0.125f * 1.4426950408889634f;        // 1/sqrt(64) * log2(e)
     // Big: 128 x 128 projections and the whole FFN as ONE kernel (ffn_fused.hpp); Ring: the 64-row ring kernels (r01 form)
     const bool big = plan.linears == LGLinears::Big;
-    auto ffn = [&](int cross, const float* w1, const float* b1, const float* lnw, const float* lnb, const float* w2,
-                   const float* b2) {
+    auto ffn = [&](int cross, const LGCtrl* ctrl, const float* w1, const float* b1, const float* lnw, const float* lnb,
+                   const float* w2, const float* b2) {
         if (big) {
             FfnKArgs k{};
             k.f.xs = act(xs, 0x20); k.f.msgs = act(msgs, 0x20); k.f.plane_rows = g->NIc * g->Kc;   // (study: the hidden planes are internal - FFN-2 keeps 3 terms here)
@@ -2181,7 +2251,7 @@ void lg_layer_h(sslam_lightglue* g, hipStream_t s, const LGPlan& plan, int NI, c
                 k.f.hc = do_stop ? g->tc_w[layer] : nullptr; k.f.hc_b = do_stop ? g->tc_b[layer] : nullptr;
                 k.f.conf_thr = conf_threshold(layer); k.f.conf = g->conf; k.f.mat = g->mat;
             }
-            k.ctrl = g->ctrl; k.Kc = g->Kc;
+            k.ctrl = ctrl; k.Kc = g->Kc;
             if (plan.merge == LGMerge::InFfn) {    // one pair, keys split into ranges: the tile merges the partials itself
                 k.f.o_part = g->o_part; k.f.m_part = g->m_part; k.f.l_part = g->l_part;
                 k.f.ks = plan.ks; k.f.part_zs = (long)g->NIc * NH * g->Kc;
@@ -2192,68 +2262,87 @@ void lg_layer_h(sslam_lightglue* g, hipStream_t s, const LGPlan& plan, int NI, c
                 hipLaunchKernelGGL(lg_ffn_fused_kernel<2>, dim3(NI * (g->Kc / 64)), dim3(512), sslam::FFN_LDS_BYTES, s, k);
             return;
         }
-        LinearArgsH a = linh(g, act(xs, 0x20), act(msgs, 0x20), D, D, 2 * D, w1, b1, 2 * D);      // [x | attention context]
+        LinearArgsH a = linh(g, ctrl, act(xs, 0x20), act(msgs, 0x20), D, D, 2 * D, w1, b1, 2 * D);      // [x | attention context]
         wgt(a, 0x80);
         a.out = g->hid; a.ldo = 2 * D;
         launch_linear_h<64, 128, 1, 2, EPH_F32>(s, NI, a);
         hipLaunchKernelGGL(lg_ln_gelu_h_kernel, dim3(tokblocks), dim3(256), 0, s, g->hid,
-                           SplitOut{g->hids_hi, g->hids_lo}, lnw, lnb, g->ctrl, g->Kc, NI, g->NIc);
-        LinearArgsH c = linh(g, act(hids, 0x20), none, 2 * D, 2 * D, 2 * D, w2, b2, D);
+                           SplitOut{g->hids_hi, g->hids_lo}, lnw, lnb, ctrl, g->Kc, NI, g->NIc);
+        LinearArgsH c = linh(g, ctrl, act(hids, 0x20), none, 2 * D, 2 * D, 2 * D, w2, b2, D);
         wgt(c, 0x80);
         c.out = g->x; c.ldo = D; c.outs = SplitOut{g->xs_hi, g->xs_lo};
         launch_linear_h<64, 64, 1, 1, EPH_RESID>(s, NI, c);
     };
     {   // self block
-        LinearArgsH a = linh(g, act(xs, 0x10), none, D, D, D, l.wqkv, l.bqkv, 3 * D);
+        LinearArgsH a = linh(g, self_ctrl, act(xs, 0x10), none, D, D, D, l.wqkv, l.bqkv, 3 * D);
         wgt(a, 0x40);
         a.q = SplitOut{g->qs_hi, g->qs_lo}; a.k = SplitOut{g->ks_hi, g->ks_lo}; a.vt = SplitOut{g->vts_hi, g->vts_lo};
         a.q_scale = sm_scale; a.k_scale = 1.0f;
         if (big) launch_linear_big<128, 128, 2, 2, EPH_QKV>(s, NI, a);
         else launch_linear_h<64, 192, 1, 3, EPH_QKV>(s, NI, a);  // 768 / 192 = 4 column tiles
     }
-    launch_attention_h(g, s, plan, NI, qs, ks, vts, 0);
-    ffn(0, l.w1, l.b1, l.lnw, l.lnb, l.w2, l.b2);
+    launch_attention_h(g, s, plan, NI, self_ctrl, qs, ks, vts, 0);
+    ffn(0, self_ctrl, l.w1, l.b1, l.lnw, l.lnb, l.w2, l.b2);
+    if (shared) {
+        const FanoutArgs a{g->x, g->enc_cos, g->enc_sin, g->xs_hi, g->xs_lo, g->Kc, g->NIc * g->Kc, g->ctrl, g->ctrl_shadow, *shared};
+        hipLaunchKernelGGL(lg_fanout_kernel, dim3(FANOUT_BLOCKS_PER_IMAGE, NI), dim3(256), 0, s, a);
+    }
     if (self_only) return;
     {   // cross block: the shared qk projection is both query and key -> sqrt(scale) on it
-        LinearArgsH a = linh(g, act(xs, 0x10), none, D, D, D, l.cqkv, l.cbqkv, 2 * D);
+        LinearArgsH a = linh(g, g->ctrl, act(xs, 0x10), none, D, D, D, l.cqkv, l.cbqkv, 2 * D);
         wgt(a, 0x40);
         a.q = SplitOut{g->qs_hi, g->qs_lo}; a.vt = SplitOut{g->vts_hi, g->vts_lo};
         a.q_scale = sqrtf(sm_scale);
         if (big) launch_linear_big<128, 128, 2, 2, EPH_CROSS>(s, NI, a);
         else launch_linear_h<64, 128, 1, 2, EPH_CROSS>(s, NI, a);
     }
-    launch_attention_h(g, s, plan, NI, qs, qs, vts, 1);
-    ffn(1, l.cw1, l.cb1, l.clnw, l.clnb, l.cw2, l.cb2);
+    launch_attention_h(g, s, plan, NI, g->ctrl, qs, qs, vts, 1);
+    ffn(1, g->ctrl, l.cw1, l.cb1, l.clnw, l.clnb, l.cw2, l.cb2);
 }
 
 // Enqueue one batch of `pairs` pairs on the context stream.  `src` names the inputs of image
 // 2p (query side) and 2p+1 of every pair; outputs of pair p go to ij_out + p*out_stride*2,
 // score_out + p*out_stride, info_out + 4p.
+// the alias table of one enqueue; `shared` = the forward takes the shared form (some image is an alias and the plan shares)
+AliasTab lg_alias_table(const LGPlan& plan, const StageSrc& src, int NI, bool& shared) {
+    AliasTab al{};
+    int rep[2 * MAX_PAIRS];
+    al.distinct = sslam::lg_alias(NI, src.xy, src.desc, src.cnt, src.bound, src.size_w, src.size_h, rep);
+    shared = plan.share_frames && al.distinct < NI;
+    for (int i = 0; i < 2 * MAX_PAIRS; ++i) al.rep[i] = (signed char)(shared && i < NI ? rep[i] : i);
+    return al;
+}
+
 int lg_enqueue(sslam_lightglue* g, int pairs, const StageSrc& src, float min_conf, int32_t* ij_out,
                float* score_out, int32_t* info_out, long out_stride) {
     hipStream_t s = g->ctx->stream;
     (void)hipGetLastError();     // (a stale error of another library on this thread - e.g. RCCL's probes - is not ours)
     const int Kc = g->Kc, NI = 2 * pairs;
     const LGPlan plan = sslam::lg_plan(g->hooks, Kc, NI, g->depth_conf > 0.0f || g->width_conf > 0.0f);
+    // shared frames: the prologue and layer 0's self block read their counts from the shadow control array (c0), where an
+    // alias image has none; without an alias c0 IS the control array and the sequence is the unshared one, launch for launch
+    bool shared = false;
+    const AliasTab al = lg_alias_table(plan, src, NI, shared);
+    const LGCtrl* const c0 = shared ? g->ctrl_shadow : g->ctrl;
     hipLaunchKernelGGL(lg_prepare_kernel, dim3(NI, 8), dim3(1024), 0, s, src, Kc, g->in_xy, g->in_desc, g->bbox,
-                       g->ind, g->prune, g->ctrl);
+                       g->ind, g->prune, g->ctrl, al, shared ? g->ctrl_shadow : nullptr);
     hipLaunchKernelGGL(lg_posenc_kernel, dim3(sslam::cdiv(NI * Kc * ENC, 256)), dim3(256), 0, s, g->in_xy,
-                       g->bbox, g->w_r, g->enc_cos, g->enc_sin, Kc, NI, g->ctrl);
+                       g->bbox, g->w_r, g->enc_cos, g->enc_sin, Kc, NI, c0);
     const bool proj_h = plan.proj_split;       // the projections and the similarity GEMM on the split pipe
     constexpr size_t big_lds = (size_t)sslam::BIG_STAGES * sslam::big_stage_halves<128, 128>() * sizeof(_Float16);
     const dim3 biggrid(D / 128, sslam::cdiv(Kc, 128), NI);
     if (proj_h) {   // input_proj: descriptors split into the (idle) k planes (k-panels), x and its planes from the epilogue
         hipLaunchKernelGGL(lg_split_rows_kernel, dim3(SPLIT_BLOCKS_PER_IMAGE, NI), dim3(256), 0, s, g->in_desc, g->ks_hi, g->ks_lo, DIN, Kc,
-                           NI, g->NIc, g->ctrl, 0);
+                           NI, g->NIc, c0, 0);
         ProjBigArgs a{};
         a.a_hi = g->ks_hi; a.a_lo = g->ks_lo; a.a_rows = g->NIc * Kc; a.K = DIN;
         a.w_hi = g->w_hi + (g->w_in - g->blob); a.w_lo = g->w_lo + (g->w_in - g->blob); a.bias = g->b_in;
         a.out_scale = 1.0f; a.out = g->x; a.o_hi = g->xs_hi; a.o_lo = g->xs_lo; a.o_rows = g->NIc * Kc;
-        a.ctrl = g->ctrl; a.Kc = Kc;
+        a.ctrl = c0; a.Kc = Kc;
         hipLaunchKernelGGL((lg_proj_big_kernel<128, 128, 2, 2>), biggrid, dim3(256), big_lds, s, a);
     } else {   // input_proj (lightglue.py: desc = self.input_proj(desc))
         LinearArgs a = lin(g, NI, g->in_desc, DIN, nullptr, 0, DIN, DIN, g->w_in, g->b_in, D);
-        a.out = g->x; a.ldo = D;
+        a.out = g->x; a.ldo = D; a.ctrl = c0;
         launch_linear<64, 64, 1, 1, EPI_PLAIN>(s, a);
     }
     const unsigned tokblocks = sslam::cdiv(NI * Kc, 4);
@@ -2261,14 +2350,14 @@ int lg_enqueue(sslam_lightglue* g, int pairs, const StageSrc& src, float min_con
     const dim3 splitblocks(SPLIT_BLOCKS_PER_IMAGE, NI);
     if (plan.split && !proj_h)
         hipLaunchKernelGGL(lg_split_rows_kernel, splitblocks, dim3(256), 0, s, g->x, g->xs_hi, g->xs_lo, D, Kc,
-                           NI, g->NIc, g->ctrl, 0);
+                           NI, g->NIc, c0, 0);
     for (int i = 0; i < plan.layers; ++i) {
         const LGLayerW& l = g->L[i];
         const bool last = i == plan.layers - 1;
         const bool self_only = plan.self_only_last && last;
         if (plan.split) {
             // the token heads of this layer (early stop + pruning) ride in the cross block's fused FFN when there is one
-            lg_layer_h(g, s, plan, NI, l, i, self_only, plan.heads_in_ffn && !last);
+            lg_layer_h(g, s, plan, NI, l, i, self_only, plan.heads_in_ffn && !last, shared && i == 0 ? &al : nullptr);
         } else {
             // ---- self block
             {
@@ -2380,13 +2469,21 @@ void lg_configure_kernels() {
     (void)hipFuncSetAttribute((const void*)lg_ffn_fused_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, sslam::FFN_LDS_BYTES);
 }
 
+// what sslam_lightglue_debug_share_info reports of the enqueue that follows
+void lg_note_sharing(sslam_lightglue* g, int pairs, const StageSrc& src) {
+    const LGPlan plan = sslam::lg_plan(g->hooks, g->Kc, 2 * pairs, g->depth_conf > 0.0f || g->width_conf > 0.0f);
+    g->last_distinct = lg_alias_table(plan, src, 2 * pairs, g->last_fanout).distinct;
+}
+
 // lg_enqueue through the graph cache (device entry points only; never while profiling: the
 // bracketing events are host-side records)
 int lg_enqueue_cached(sslam_lightglue* g, int pairs, const StageSrc& src, float min_conf, int32_t* ij_out,
                       float* score_out, int32_t* info_out, long out_stride) {
     g->last_pairs = pairs;                 // host-side bookkeeping lives OUTSIDE the captured sequence (a replay skips the lambda)
+    lg_note_sharing(g, pairs, src);
     if (!g->use_graphs || g->profile)
         return lg_enqueue(g, pairs, src, min_conf, ij_out, score_out, info_out, out_stride);
+    // the key holds every field lg_alias compares (pointers, bound, size of every image): one cached graph, one alias structure
     std::vector<uint64_t> key{(uint64_t)pairs, (uint64_t)ij_out, (uint64_t)score_out, (uint64_t)info_out,
                               (uint64_t)out_stride, 0};
     memcpy(&key[5], &min_conf, sizeof(float));
@@ -2425,7 +2522,7 @@ int sslam_lightglue_create_batched(sslam_ctx* ctx, const float* weights, size_t 
     const size_t K = (size_t)Kc, NI = (size_t)g->NIc, NB = (size_t)max_pairs;
     auto carve = [&](sslam::Arena& A) {
         g->blob = A.take<float>(n_floats);
-        g->ctrl = A.take<LGCtrl>(NB);
+        g->ctrl = A.take<LGCtrl>(NB); g->ctrl_shadow = A.take<LGCtrl>(NB);
         g->range_sticky = A.take<int>(4);
         g->x = A.take<float>(NI * K * D); g->msg = A.take<float>(NI * K * D);
         g->tx = A.take<float>(NI * K * D); g->md = A.take<float>(NI * K * D);
@@ -2602,6 +2699,7 @@ int sslam_lightglue_match_host_sized(sslam_lightglue* g, const float* xy0, const
     if (size0) { src.size_w[0] = size0[0]; src.size_h[0] = size0[1]; }
     if (size1) { src.size_w[1] = size1[0]; src.size_h[1] = size1[1]; }
     g->last_pairs = 1;
+    lg_note_sharing(g, 1, src);
     if (int rc = lg_enqueue(g, 1, src, min_conf, g->out_ij, g->out_score, g->out_info, (long)K)) return rc;
     int32_t info[4];
     SSLAM_HIP_CHECK(hipMemcpyAsync(info, g->out_info, sizeof(info), hipMemcpyDeviceToHost, s));
@@ -2738,6 +2836,24 @@ int sslam_lightglue_debug_split_form(sslam_lightglue* g, int mask) {
         SSLAM_HIP_CHECK(hipMemset(g->zero_plane, 0, n));
     }
     g->hooks.study = mask;
+    return 0;
+}
+
+/* Test hook: 1 (default) = a frame that several images of one enqueue name (equal source pointers, bound and size) runs the
+ * prologue and the self block of layer 0 once and lg_fanout_kernel copies its state to the other images; 0 = every image is
+ * computed.  Results are bit-identical.  The fp32 path (precision 0) always computes every image. */
+int sslam_lightglue_debug_share_frames(sslam_lightglue* g, int enable) {
+    SSLAM_REQUIRE(g != nullptr && (enable == 0 || enable == 1), "sslam_lightglue_debug_share_frames: bad argument");
+    g->settings_changed();
+    g->hooks.share_frames = enable != 0;
+    return 0;
+}
+
+/* Test hook: what the last enqueue did with shared frames: out[0] = its distinct images (lg_alias), out[1] = 1 when its launch
+ * sequence holds lg_fanout_kernel (some image was an alias and the shared form is on), else 0. */
+int sslam_lightglue_debug_share_info(sslam_lightglue* g, int32_t* out) {
+    SSLAM_REQUIRE(g && out, "sslam_lightglue_debug_share_info: NULL argument");
+    out[0] = g->last_distinct; out[1] = g->last_fanout ? 1 : 0;
     return 0;
 }
 

@@ -146,6 +146,19 @@ class LightGlueHIP:
         self.epoch += 1
         _native.check(_native.lib().sslam_lightglue_debug_big_gemm(self.handle, int(mode)))
 
+    def debug_share_frames(self, enable: bool = True):
+        """Test hook: True (default) a frame that several images of one enqueue name (equal source pointers, bound and
+        size) runs the prologue and layer 0's self block once and a copy kernel fans its state out; False every image
+        is computed.  Bit-identical results."""
+        self.epoch += 1
+        _native.check(_native.lib().sslam_lightglue_debug_share_frames(self.handle, int(bool(enable))))
+
+    def debug_share_info(self):
+        """(distinct images of the last enqueue, whether its launch sequence holds the fan-out copy)."""
+        out = (C.c_int32 * 2)()
+        _native.check(_native.lib().sslam_lightglue_debug_share_info(self.handle, out))
+        return int(out[0]), bool(out[1])
+
     def debug_read(self, which: int, shape, dtype=np.float32):
         out = np.empty(shape, dtype)
         _native.check(_native.lib().sslam_lightglue_debug_read(self.handle, which, _native.ptr(out), out.nbytes))
