@@ -259,6 +259,24 @@ int sslam_two_view_metrics_host(sslam_ctx* ctx, int n, const float* pts1, const 
                                 const unsigned char* sel, const double* K9, const double* R9, const double* t3,
                                 double* metrics_out, int32_t* info_out, double* X_out, double* z_out);
 
+/* ------------------------------------------------------- homography RANSAC
+ * Replaces `cv2.findHomography(pts1, pts2, cv2.RANSAC, thresh)` as the two-view gate calls it
+ * (slam/core/two_view_bootstrap.py:230, :294; the tracking fallbacks slam/monocular/main.py:409, main4.py:458): OpenCV 4.x's
+ * classic path - 4-point normalised DLT, cv::RNG sample stream, collinearity and orientation tests on every draw, float error
+ * of the forward transfer, the loop's mask kept, then one DLT on the inliers and at most 10 Levenberg-Marquardt iterations
+ * on H's first eight entries.  fp64 (the error in float, as in OpenCV).  Parity with cv2 itself is unpinned
+ * (tests/homography_ref.py names what could not be confirmed).
+ *   pts1, pts2 : float32 [n][2] source / destination pixels (host), 4 <= n <= 16384 (anything else is an error);
+ *   n == 4: one DLT on the four matches, mask all ones, no refinement
+ *   thresh <= 0 -> 3, confidence outside (0,1) -> 0.995, max_iters clamped to [1, 2000]
+ *   mask_out[n] : 1 = inlier of the loop's winning sample;  H_out[9] (may be NULL): row-major, H[8] = 1, zeros without a model
+ *   info_out[4] (may be NULL): inliers (-1: no model, cv2 would return (None, None)), iterations the sequential loop
+ *                              runs (0 for n == 4), 0, winning sample
+ * Two calls on the same input give the same bits. */
+int sslam_homography_ransac_host(sslam_ctx* ctx, int n, const float* pts1, const float* pts2, double thresh,
+                                 double confidence, int max_iters, unsigned char* mask_out, double* H_out,
+                                 int32_t* info_out);
+
 /* ------------------------------------------- 2D-3D association for tracking
  * Replaces the per-point loop of `reproject_and_match_2d3d` (slam/core/pnp_utils.py:224-304) for
  * float descriptors: projection (`_project_points` :127-141), radius search (cKDTree :238, :265),

@@ -1,4 +1,5 @@
-// geom_common.hpp - device helpers shared by the geometry kernels (ransac_kernels.hip, pnp_kernels.hip, ba_lm.hip).
+// geom_common.hpp - device helpers shared by the geometry kernels (ransac_kernels.hip, homography_kernels.hip,
+// pnp_kernels.hip, ba_lm.hip).
 //
 // The RANSAC pieces restate OpenCV 4.x's classic ptsetreg.cpp; both RANSAC files must stay bit-exact with the numpy
 // restatements under oracle/, so they share one copy.  Nothing here holds a contractible multiply-add: pnp_kernels.hip
@@ -49,6 +50,21 @@ __device__ __forceinline__ void draw_distinct(CvRng& rng, int n, int* idx) {
     }
 }
 
+// haveCollinearPoints(m, count) of fundam.cpp: the LAST point of the subset against every earlier pair, on points p [.][2]
+__device__ inline bool last_point_collinear(const float* p, const int* idx, int count) {
+    const int i = count - 1;
+    const float xi = p[2 * idx[i]], yi = p[2 * idx[i] + 1];
+    for (int j = 0; j < i; ++j) {
+        const double dx1 = p[2 * idx[j]] - xi, dy1 = p[2 * idx[j] + 1] - yi;
+        for (int k = 0; k < j; ++k) {
+            const double dx2 = p[2 * idx[k]] - xi, dy2 = p[2 * idx[k] + 1] - yi;
+            if (fabs(dx2 * dy1 - dy2 * dx1) <= (double)FLT_EPSILON * (fabs(dx1) + fabs(dy1) + fabs(dx2) + fabs(dy2)))
+                return true;
+        }
+    }
+    return false;
+}
+
 // Fixed-order tree reduction in LDS over a power-of-two workgroup: NT threads when the launch fixes it, else blockDim.x.
 // Every thread calls it and gets the result; `sh` holds one element per thread.
 // `op(acc, v)` folds v into acc in place.
@@ -71,6 +87,29 @@ __device__ __forceinline__ T block_sum(T v, T* sh) { return block_reduce<NT>(v, 
 template <int NT = 0>
 __device__ __forceinline__ double block_max(double v, double* sh) {
     return block_reduce<NT>(v, sh, [](double& acc, double x) { acc = fmax(acc, x); });
+}
+
+// N sums at once over a workgroup of NT threads (a multiple of 64; every thread calls it), two barriers for all of them: a
+// wave's lanes by xor-shuffles, then thread k adds sum k of the waves in wave order - a fixed order.  `part` (NT / 64 x N
+// doubles) and `out` (N doubles, the result, valid for every thread on return) are LDS.
+template <int NT, int N>
+__device__ __forceinline__ void block_sum_n(const double (&acc)[N], double* part, double* out) {
+    static_assert(N <= NT, "one thread per sum");
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        double v = acc[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == 0) part[w * N + k] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < N) {
+        double s = 0;
+        for (int j = 0; j < NT / 64; ++j) s += part[j * N + threadIdx.x];
+        out[threadIdx.x] = s;
+    }
+    __syncthreads();
 }
 
 // One turn of an order-preserving compaction over a workgroup of NT threads (a multiple of 64; every thread calls it):

@@ -74,21 +74,6 @@ struct RSArgs {
 
 __device__ __forceinline__ int rs_n(const RSArgs& a) { return a.n_dev ? min(max(a.n_dev[0], 0), a.n) : a.n; }
 
-// haveCollinearPoints(m, count): last point against every earlier pair
-__device__ bool last_point_collinear(const float* p, const int* idx, int count) {
-    const int i = count - 1;
-    const float xi = p[2 * idx[i]], yi = p[2 * idx[i] + 1];
-    for (int j = 0; j < i; ++j) {
-        const double dx1 = p[2 * idx[j]] - xi, dy1 = p[2 * idx[j] + 1] - yi;
-        for (int k = 0; k < j; ++k) {
-            const double dx2 = p[2 * idx[k]] - xi, dy2 = p[2 * idx[k] + 1] - yi;
-            if (fabs(dx2 * dy1 - dy2 * dx1) <= (double)FLT_EPSILON * (fabs(dx1) + fabs(dy1) + fabs(dx2) + fabs(dy2)))
-                return true;
-        }
-    }
-    return false;
-}
-
 // ---- 1. replay the sample stream for samples [h0, h1) (one lane) ------------------------------
 // r05: the lane's collinearity tests read 2 x 7 points per attempt - dependent global loads, ~3 us per sample, 50 us for the
 // 16-sample first chunk that is all a matcher's inlier ratios ever need.  The workgroup now copies both point sets into LDS
@@ -114,7 +99,7 @@ __device__ void rs_subsets_step(const RSArgs& a, int h0, int h1, float* rs_pts, 
     const float* p2 = in_lds ? rs_pts + 2 * n : a.p2;
     // haveCollinearPoints tests the LAST point of the subset against every earlier pair (j, k < j): 15 pairs x 2 point sets =
     // 30 independent tests, one per lane (a single lane spent ~1 200 instructions per sample on them, most of the 46 us of the
-    // first chunk); the verdict is their OR, as in last_point_collinear
+    // first chunk); the verdict is their OR, as in sslam::last_point_collinear
     const int q = lane % 15, set = lane / 15;
     int tj = 1, tk = 0;
     for (int t = 0; t < q; ++t) { if (++tk == tj) { ++tj; tk = 0; } }        // q -> (j, k): (1,0) (2,0) (2,1) (3,0) ...

@@ -1,9 +1,9 @@
 """The one name `triangulation_utils` takes from the reference's `slam/core/two_view_bootstrap.py`:
 `pts_from_matches` (:415-418), so that importing the overlay's triangulation never reaches `cv2`.
 
-The two-view bootstrap itself - homography / essential-matrix RANSAC, `decomposeHomographyMat`, `recoverPose`, the model
-selection around them - is OUT OF SCOPE of this backend and is not here: a driver that bootstraps a map keeps the
-reference's module for that (it needs OpenCV) and patches in only the names it wants from this overlay.
+The two-view bootstrap itself is not here but in two modules of its own, `two_view_pose` (the F/E leg, the scores, the map
+building) and `two_view_gate` (homography RANSAC, `decomposeHomographyMat`, the model selection): a driver patches their
+names into the module it bootstraps with, and this one stays importable on its own.
 """
 from __future__ import annotations
 

@@ -13,9 +13,9 @@ and, in plain numpy, the residuals and scores around them (`sampson_distances_F`
 
 This is a module of its own because the overlay's `two_view_bootstrap` holds `pts_from_matches` and nothing else (a driver
 without OpenCV installs that one whole); these names are patched into the REFERENCE's `two_view_bootstrap` one by one
-(INTEGRATION section 2), which keeps what is out of scope here: homography RANSAC, `decomposeHomographyMat`,
-`recover_pose_from_homography`, `evaluate_two_view_bootstrap*`.  So `bootstrap_two_view_map` needs its `decision`: without
-one it raises instead of running a gate this backend does not have.
+(INTEGRATION section 2); the gate itself - homography RANSAC, `decomposeHomographyMat`,
+`recover_pose_from_homography`, `evaluate_two_view_bootstrap*` - is `two_view_gate`, which imports this module.  This
+module's `bootstrap_two_view_map` needs its `decision`: without one it raises (the gate's function of that name runs the gate).
 """
 from __future__ import annotations
 
