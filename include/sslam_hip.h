@@ -277,6 +277,29 @@ int sslam_homography_ransac_host(sslam_ctx* ctx, int n, const float* pts1, const
                                  double confidence, int max_iters, unsigned char* mask_out, double* H_out,
                                  int32_t* info_out);
 
+/* ---------------------------------------------------- essential-matrix RANSAC
+ * Replaces `cv2.findEssentialMat(pts0, pts1, K, cv2.RANSAC, 0.999, thresh)` as the tracking-lost fallback calls it
+ * (slam/monocular/main_revamped.py:512, main.py:402, main4.py:457): OpenCV 4.x's classic path - pixels widened to double
+ * and normalised (x - cx) / fx, (y - cy) / fy, the threshold divided by (fx + fy) / 2, the cv::RNG sample stream (five
+ * distinct indices, no subset test), Nister's five-point solver (up to ten models per sample, each of unit Frobenius norm,
+ * scored in order), the Sampson distance in double stored as float, the budget re-estimated after every improvement, no
+ * refit and no polish.  fp64.  Parity with cv2 itself is unpinned (tests/essential_ref.py names what could not be
+ * confirmed).  The mask and E feed `sslam_recover_pose_host` as they are.
+ *   pts1, pts2 : float32 [n][2] matched pixels (host), 5 <= n <= 16384 (anything else is an error);
+ *   n == 5: one solve on the five matches, mask all ones, every model returned
+ *   K9 : row-major 3x3 (fx, fy, cx, cy are read)
+ *   prob outside (0,1) -> 0.999, thresh <= 0 -> 1, max_iters <= 0 -> 1000, above 2000 -> 2000 (the scratch slab holds
+ *   max_iters x 10 models)
+ *   mask_out[n] : 1 = inlier of the winning model;  E_out[90] (may be NULL): the winner row-major in E_out[0..9), the
+ *   rest zero; for n == 5 every model, stacked; zeros without a model
+ *   info_out[4] (may be NULL): inliers (-1: no model, cv2 would return (None, None)), iterations the sequential loop
+ *                              runs (0 for n == 5), the winning model's index within its sample (for n == 5 the number
+ *                              of models), winning sample
+ * Two calls on the same input give the same bits. */
+int sslam_essential_ransac_host(sslam_ctx* ctx, int n, const float* pts1, const float* pts2, const double* K9,
+                                double prob, double thresh, int max_iters, unsigned char* mask_out,
+                                double* E_out, int32_t* info_out);
+
 /* ------------------------------------------- 2D-3D association for tracking
  * Replaces the per-point loop of `reproject_and_match_2d3d` (slam/core/pnp_utils.py:224-304) for
  * float descriptors: projection (`_project_points` :127-141), radius search (cKDTree :238, :265),

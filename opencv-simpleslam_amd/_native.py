@@ -68,6 +68,7 @@ def _signatures():
         "sslam_recover_pose_host": (i32, [vp, i32, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp]),
         "sslam_two_view_metrics_host": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "sslam_homography_ransac_host": (i32, [vp, i32, vp, vp, C.c_double, C.c_double, i32, vp, vp, vp]),
+        "sslam_essential_ransac_host": (i32, [vp, i32, vp, vp, vp, C.c_double, C.c_double, i32, vp, vp, vp]),
         "sslam_reproject_match_host": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, C.c_double, C.c_double,
                                              vp, vp, vp]),
         "sslam_reproject_match_dev": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, C.c_double, C.c_double,

@@ -84,3 +84,15 @@ def two_view_metrics(K, R, t, pts1, pts2, sel=None, want_points: bool = False, c
         out += ({"in_front": int(info[1])},)
     return out
 
+
+def relative_pose_2d2d(pts0, pts1, K, thresh: float, prob: float = 0.999, ctx=None):
+    """The tracking-lost fallback's two calls chained (slam/monocular/main_revamped.py:512-514, main.py:402, main4.py:457):
+    `E, inlE = cv2.findEssentialMat(pts0, pts1, K, cv2.RANSAC, prob, thresh)`, then, when there is an E whose mask has at
+    least five ones, `cv2.recoverPose(E, pts0, pts1, K, mask=inlE)`.  Returns (inliers, R [3,3], t [3,1], mask uint8
+    [n,1]), or (0, None, None, None) when the reference's guard fails.  Exactly five matches give a stack of models that
+    cv2.recoverPose does not take: the empty result as well.  The pose scaling and composition stay the driver's."""
+    from . import essential
+    E, inl, _ = essential.find_essential_mat_ransac(pts0, pts1, K, prob, thresh, ctx=ctx)
+    if E is None or inl is None or int(inl.sum()) < 5 or E.shape != (3, 3):
+        return 0, None, None, None
+    return recover_pose(E, pts0, pts1, K, mask=inl, ctx=ctx)
