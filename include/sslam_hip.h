@@ -300,6 +300,31 @@ int sslam_essential_ransac_host(sslam_ctx* ctx, int n, const float* pts1, const 
                                 double prob, double thresh, int max_iters, unsigned char* mask_out,
                                 double* E_out, int32_t* info_out);
 
+/* ------------------------------------------------------- lens undistortion
+ * Replaces `cv2.initUndistortRectifyMap(K, D, None, new_K, (W0, H0), cv2.CV_32FC1)` and the per-frame
+ * `cv2.remap(img, mapx, mapy, cv2.INTER_LINEAR)` (slam/monocular/main_revamped.py:311-316, :324): the maps are computed
+ * once on the device in fp64 (OpenCV's model: inv(newK R), the rational radial factor, two tangential terms; rounded to
+ * float32), turned into cv2.convertMaps' fixed-point form (int16 pixel + 5-bit fractions, round half to even; a non-finite
+ * coordinate or one beyond the int32 range of v * 32 becomes a record outside every source) and kept there; a remap is one
+ * integer-only gather kernel: weights (32 - fx)(32 - fy) 32 ... that sum to 2^15, dst = (sum + 2^14) >> 15, every sample
+ * outside the source counts as 0 (BORDER_CONSTANT, value 0).  Parity with cv2 itself is unpinned (tests/undistort_ref.py
+ * names what could not be confirmed). */
+typedef struct sslam_undistort sslam_undistort;
+/* cv2.initUndistortRectifyMap(K, D, R, newK, (W, H), CV_32FC1), then cv2.convertMaps' fixed-point form, kept on the device.
+ * D: n_dist in {0, 4, 5, 8} doubles (k1 k2 p1 p2 [k3 [k4 k5 k6]]); R9 NULL = identity; 1 <= W, H <= 16384. */
+int sslam_undistort_create(sslam_ctx* ctx, const double* K9, const double* D, int n_dist, const double* R9,
+                           const double* newK9, int W, int H, sslam_undistort** out);
+/* the same instance from the caller's float32 maps [H][W] (host): cv2.remap(img, mapx, mapy, INTER_LINEAR) with any maps */
+int sslam_undistort_create_from_maps(sslam_ctx* ctx, const float* mapx, const float* mapy, int W, int H,
+                                     sslam_undistort** out);
+int sslam_undistort_destroy(sslam_undistort* u);
+/* any pointer may be NULL: float32 maps [H*W]; ixy int16 [H*W*2]; alpha uint16 [H*W] (= fy * 32 + fx) */
+int sslam_undistort_maps_read(sslam_undistort* u, float* mapx, float* mapy, int16_t* ixy, uint16_t* alpha);
+/* src uint8 [Hs][Ws][C], C in {1, 3, 4}, 1 <= Hs, Ws <= 16384; dst uint8 [H][W][C]; BORDER_CONSTANT, value 0.
+ * _dev: device pointers, dst 16-byte aligned (as sslam_malloc returns it); enqueue only. */
+int sslam_undistort_remap_host(sslam_undistort* u, const uint8_t* src, int Hs, int Ws, int C, uint8_t* dst);
+int sslam_undistort_remap_dev(sslam_undistort* u, const uint8_t* src, int Hs, int Ws, int C, uint8_t* dst);
+
 /* ------------------------------------------- 2D-3D association for tracking
  * Replaces the per-point loop of `reproject_and_match_2d3d` (slam/core/pnp_utils.py:224-304) for
  * float descriptors: projection (`_project_points` :127-141), radius search (cKDTree :238, :265),

@@ -69,6 +69,12 @@ def _signatures():
         "sslam_two_view_metrics_host": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "sslam_homography_ransac_host": (i32, [vp, i32, vp, vp, C.c_double, C.c_double, i32, vp, vp, vp]),
         "sslam_essential_ransac_host": (i32, [vp, i32, vp, vp, vp, C.c_double, C.c_double, i32, vp, vp, vp]),
+        "sslam_undistort_create": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, c_void_pp]),
+        "sslam_undistort_create_from_maps": (i32, [vp, vp, vp, i32, i32, c_void_pp]),
+        "sslam_undistort_destroy": (i32, [vp]),
+        "sslam_undistort_maps_read": (i32, [vp, vp, vp, vp, vp]),
+        "sslam_undistort_remap_host": (i32, [vp, vp, i32, i32, i32, vp]),
+        "sslam_undistort_remap_dev": (i32, [vp, vp, i32, i32, i32, vp]),
         "sslam_reproject_match_host": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, C.c_double, C.c_double,
                                              vp, vp, vp]),
         "sslam_reproject_match_dev": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, C.c_double, C.c_double,

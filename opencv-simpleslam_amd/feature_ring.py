@@ -34,7 +34,7 @@ from itertools import compress
 
 import numpy as np
 
-from . import _native, epipolar
+from . import _native, epipolar, undistort
 from .slam.core.types import (KeyPointList, MatchList, bind_matches, dmatch_edit_epoch, keypoint_shells, keypoints_from_xy,
                               match_shells, matches_from_ij, xy_from_keypoints)
 
@@ -121,7 +121,7 @@ class DeviceFeatureRing:
         self.kf_next = None              # a frame the loop has just promoted (its keyframe pair was asked twice)
         self.kf_asked_seq = -1           # seq of the newest frame a keyframe match was asked for
         self.kf_gap = None               # frames between a keyframe and the first match against it (the loop's cooldown + 1)
-        self.stats = dict(resident=0, memo=0, ahead=0, ahead_kf=0, reupload=0, wasted=0)
+        self.stats = dict(resident=0, memo=0, ahead=0, ahead_kf=0, reupload=0, wasted=0, upload_skipped=0)
 
     def attach_matcher(self, matcher):
         self._resolve_masks()
@@ -221,7 +221,10 @@ class DeviceFeatureRing:
             H, Wd, Cn = img.shape
         else:
             raise ValueError(f"unsupported image shape {img.shape}")
-        if img.nbytes > self.img_cap:
+        # the array an `Undistorter` of this context returned last (read-only, so still what the device holds): extract from its
+        # device copy, no upload
+        und_dev = undistort.device_copy(img, ctx)
+        if und_dev is None and img.nbytes > self.img_cap:
             if self.img_dev:
                 ctx.sync(); ctx.free(self.img_dev)
             self.img_cap = max(img.nbytes, 1241 * 376 * 3)
@@ -236,10 +239,14 @@ class DeviceFeatureRing:
         K = self.K
         # (the image goes up straight from the caller's pageable array: the runtime's own staged copy, 69 us for
         #  1.4 MB, beats a host copy into a page-locked stage + DMA, 57 + 41 us)
-        staged = np.ascontiguousarray(img)   # (a non-contiguous image: this copy must outlive the DMA - it is held until the ctx.sync() below)
-        ctx.h2d_async(self.img_dev, staged)  # (pageable source: the runtime stages it before the call returns; page-locked: the DMA reads it in place)
+        staged = None
+        if und_dev is None:
+            staged = np.ascontiguousarray(img)   # (a non-contiguous image: this copy must outlive the DMA - it is held until the ctx.sync() below)
+            ctx.h2d_async(self.img_dev, staged)  # (pageable source: the runtime stages it before the call returns; page-locked: the DMA reads it in place)
+        else:
+            self.stats["upload_skipped"] += 1
         prev = self.last
-        det.extract_dev(self.img_dev, H, Wd, Cn, sl["xy"], sl["desc"], sl["score"], sl["cnt"], max_kpts=K)
+        det.extract_dev(self.img_dev if und_dev is None else und_dev, H, Wd, Cn, sl["xy"], sl["desc"], sl["score"], sl["cnt"], max_kpts=K)
         ctx.record(self.ev_extracted)
         ctx.d2h_async(self.pin_rec, sl["base"])
         look = (self.ahead_on and self.matcher is not None and prev is not None and prev.slot is not None
