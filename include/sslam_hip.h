@@ -325,6 +325,54 @@ int sslam_undistort_maps_read(sslam_undistort* u, float* mapx, float* mapy, int1
 int sslam_undistort_remap_host(sslam_undistort* u, const uint8_t* src, int Hs, int Ws, int C, uint8_t* dst);
 int sslam_undistort_remap_dev(sslam_undistort* u, const uint8_t* src, int Hs, int Ws, int C, uint8_t* dst);
 
+/* ------------------------------------------------ pyramidal Lucas-Kanade
+ * Replaces `cv2.cvtColor(img, cv2.COLOR_BGR2GRAY)` and `cv2.calcOpticalFlowPyrLK(prev, next, pts, None, winSize, maxLevel,
+ * criteria, flags, minEigThreshold)` for 8-bit images, and the forward-backward gate of the KLT front end
+ * (slam/monocular/main4.py:396-433).  An instance keeps the pyramids of two frames on the device: grey, the pyrDown levels
+ * (padded by winSize, BORDER_REFLECT_101) and the unscaled int16 Scharr pair of every level (padded with zeros); a push builds
+ * one frame's pyramid ONCE and the frame that was "current" becomes "previous".  The tracker is OpenCV's fixed-point scheme
+ * (2^14 bilinear weights, int16 patches); its window sums are exact integers converted to float32 once.  Parity with cv2
+ * itself is unpinned (tests/klt_ref.py names what could not be confirmed).
+ * Limits: 1 <= w, h <= 16384; window sides odd, 3..31 (the patch of one point is held in LDS; the integer sums stay below 2^53
+ * and are exact); maxLevel 0..10; 1 <= n <= max_points <= 2^20. */
+typedef struct sslam_klt sslam_klt;
+int sslam_klt_create(sslam_ctx* ctx, int max_w, int max_h, int max_points, int win_w, int win_h, int max_level,
+                     sslam_klt** out);
+int sslam_klt_destroy(sslam_klt* k);
+/* img uint8 [h][w][c], c in {1, 3 (BGR), 4 (BGRA)}, w <= max_w, h <= max_h.  _host returns when the image has been read;
+ * _dev: device pointer, enqueue only (the image must stay untouched until the stream has passed the call). */
+int sslam_klt_push_host(sslam_klt* k, const uint8_t* img, int h, int w, int c);
+int sslam_klt_push_dev(sslam_klt* k, const uint8_t* img, int h, int w, int c);
+/* the grey conversion alone: gray uint8 [h][w] (host) */
+int sslam_klt_gray_host(sslam_ctx* ctx, const uint8_t* img, int h, int w, int c, uint8_t* gray);
+/* previous -> current (reverse = 0) or current -> previous (reverse = 1).  prev_pts [n][2] float32; init_pts [n][2] is read
+ * under OPTFLOW_USE_INITIAL_FLOW (flags & 4) and may be NULL otherwise; flags & 8 = OPTFLOW_LK_GET_MIN_EIGENVALS;
+ * (criteria_type, max_count, epsilon) as cv2's TermCriteria (COUNT = 1, EPS = 2; clamped as OpenCV clamps them).
+ * Out: next_pts [n][2] float32, status [n] uint8, err [n] float32 (0 where OpenCV leaves it unwritten).
+ * _dev: device pointers, enqueue only. */
+int sslam_klt_track_host(sslam_klt* k, int reverse, int n, const float* prev_pts, const float* init_pts, int flags,
+                         int criteria_type, int max_count, double epsilon, double min_eig_threshold, float* next_pts,
+                         uint8_t* status, float* err);
+int sslam_klt_track_dev(sslam_klt* k, int reverse, int n, const float* prev_pts, const float* init_pts, int flags,
+                        int criteria_type, int max_count, double epsilon, double min_eig_threshold, float* next_pts,
+                        uint8_t* status, float* err);
+/* main4.py:402-433 in one call: forward, backward from the forward result (all points), the masks status == 1,
+ * err < err_thresh, st_back == 1 && |back - prev| < fb_thresh (float32, thresholds rounded to float32), and the kept pairs
+ * compacted in point order.  Out: pts0 / pts1 [n][2] float32 of which the first counts[4] pairs are written;
+ * counts[5] = raw, st1, err_ok, fb_ok, kept; optional (may be NULL) next_pts [n][2] and mask [n] uint8 (bit 0 status,
+ * bit 1 err, bit 2 forward-backward, bit 3 kept).  _dev: device pointers, everything stays on the device, enqueue only. */
+int sslam_klt_track_fb_host(sslam_klt* k, int n, const float* prev_pts, int criteria_type, int max_count, double epsilon,
+                            double min_eig_threshold, double err_thresh, double fb_thresh, float* next_pts, float* pts0,
+                            float* pts1, int* counts, uint8_t* mask);
+int sslam_klt_track_fb_dev(sslam_klt* k, int n, const float* prev_pts, int criteria_type, int max_count, double epsilon,
+                           double min_eig_threshold, double err_thresh, double fb_thresh, float* next_pts, float* pts0,
+                           float* pts1, int* counts, uint8_t* mask);
+/* test hooks.  info: the effective maxLevel and the size of the current (previous = 0) or previous (1) frame.
+ * levels_read: one level of it back to the host, any pointer may be NULL: img uint8 [h_l][w_l] (level 0 is the grey image),
+ * dx / dy int16 [h_l][w_l]. */
+int sslam_klt_info(sslam_klt* k, int previous, int* top_level, int* w, int* h);
+int sslam_klt_levels_read(sslam_klt* k, int previous, int level, uint8_t* img, int16_t* dx, int16_t* dy);
+
 /* ------------------------------------------- 2D-3D association for tracking
  * Replaces the per-point loop of `reproject_and_match_2d3d` (slam/core/pnp_utils.py:224-304) for
  * float descriptors: projection (`_project_points` :127-141), radius search (cKDTree :238, :265),

@@ -75,6 +75,17 @@ def _signatures():
         "sslam_undistort_maps_read": (i32, [vp, vp, vp, vp, vp]),
         "sslam_undistort_remap_host": (i32, [vp, vp, i32, i32, i32, vp]),
         "sslam_undistort_remap_dev": (i32, [vp, vp, i32, i32, i32, vp]),
+        "sslam_klt_create": (i32, [vp, i32, i32, i32, i32, i32, i32, c_void_pp]),
+        "sslam_klt_destroy": (i32, [vp]),
+        "sslam_klt_push_host": (i32, [vp, vp, i32, i32, i32]),
+        "sslam_klt_push_dev": (i32, [vp, vp, i32, i32, i32]),
+        "sslam_klt_gray_host": (i32, [vp, vp, i32, i32, i32, vp]),
+        "sslam_klt_track_host": (i32, [vp, i32, i32, vp, vp, i32, i32, i32, C.c_double, C.c_double, vp, vp, vp]),
+        "sslam_klt_track_dev": (i32, [vp, i32, i32, vp, vp, i32, i32, i32, C.c_double, C.c_double, vp, vp, vp]),
+        "sslam_klt_track_fb_host": (i32, [vp, i32, vp, i32, i32] + [C.c_double] * 4 + [vp] * 5),
+        "sslam_klt_track_fb_dev": (i32, [vp, i32, vp, i32, i32] + [C.c_double] * 4 + [vp] * 5),
+        "sslam_klt_info": (i32, [vp, i32, c_int_p, c_int_p, c_int_p]),
+        "sslam_klt_levels_read": (i32, [vp, i32, i32, vp, vp, vp]),
         "sslam_reproject_match_host": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, C.c_double, C.c_double,
                                              vp, vp, vp]),
         "sslam_reproject_match_dev": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, C.c_double, C.c_double,
