@@ -2430,7 +2430,9 @@ int sslam_aliked_extract_host(sslam_aliked* g, const uint8_t* img, int H, int W,
 }
 
 /* Test hook.  which: 0 = score map [h][w], 1 = kp_index [n] (int32), 2 = dims {h,w,Hp,Wp,pl,pt,n_cand,n_kp},
- * 3 = x1 [16][Hp][Wp], 4 = x2, 5 = x3, 6 = x4, 7 = img [3][Hp][Wp], 8 = nms [h][w], 9 = kp_norm [n][2] */
+ * 3 = x1 [16][Hp][Wp], 4 = x2, 5 = x3, 6 = x4, 7 = img [3][Hp][Wp], 8 = nms [h][w], 9 = kp_norm [n][2],
+ * 10 = g1 channel-last [Hp][Wp][32], 11 = rnorm [Hp][Wp], 12..14 = g2..g4 planar, 15..17 = pre2..pre4 [13][level pixels],
+ * 18 = s8 [8][Hp][Wp], 19 = pos [n][16][2], 20 = patch [n][1152].  Frame 0 of a batch; all read-only. */
 int sslam_aliked_debug_read(sslam_aliked* g, int which, void* dst, size_t bytes) {
     SSLAM_REQUIRE(g && dst, "sslam_aliked_debug_read: NULL argument");
     SSLAM_HIP_CHECK(hipStreamSynchronize(g->ctx->stream));
@@ -2466,6 +2468,8 @@ int sslam_aliked_debug_read(sslam_aliked* g, int which, void* dst, size_t bytes)
         case 16: src = g->pre3; cap = AGG_PRE * HWp / 64 * 4; break;
         case 17: src = g->pre4; cap = AGG_PRE * HWp / 1024 * 4; break;
         case 18: src = g->s8; cap = 8 * HWp * 4; break;
+        case 19: src = g->pos; cap = (size_t)g->max_kpts * 32 * 4; break;      // SDDH sample positions [n][16][2], un-padded pixels (x, y)
+        case 20: src = g->patch; cap = (size_t)g->max_kpts * 1152 * 4; break;  // SDDH 3 x 3 patches [n][c * 9 + tap]
         default: SSLAM_REQUIRE(false, "sslam_aliked_debug_read: unknown buffer %d", which);
     }
     SSLAM_REQUIRE(bytes <= cap, "sslam_aliked_debug_read: %zu bytes requested, buffer has %zu", bytes, cap);
