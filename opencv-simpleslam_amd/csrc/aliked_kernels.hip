@@ -17,6 +17,7 @@
 //   s8 [8][Hp][Wp]       first score-head layer  rnorm [Hp][Wp] 1/||F||
 //   score [h][w]         un-padded score map     nms [h][w]
 #include "common.hpp"
+#include "al_plan.hpp"
 #include "gemm_f32.hpp"
 #include <type_traits>
 #include "gemm_f16x3.hpp"
@@ -28,6 +29,11 @@ using sslam::acc_row;
 using sslam::GemmSmem;
 using sslam::GemmA;
 using sslam::gemm_mainloop;
+// the network-size bookkeeping and every shape constant the host arithmetic shares with the kernels: al_plan.hpp
+using sslam::Dims;
+using sslam::MAX_FRAMES; using sslam::B1_SW; using sslam::B2_SW; using sslam::DCN3_CS; using sslam::DCN4_CS; using sslam::AGG_PRE;
+using sslam::ST_W; using sslam::ST_H; using sslam::NHALO; using sslam::NW_R; using sslam::NW_OW; using sslam::NW_OH; using sslam::HBINS;
+using sslam::COLLECT_PPT; using sslam::SEL_CAP; using sslam::EDGE_CAP; using sslam::REFINE_KPB; using sslam::SDDH_KSPLIT;
 
 constexpr float SELU_SCALE = 1.0507009873554804934193349852946f;
 constexpr float SELU_ALPHA = 1.6732632423543772848170429916717f;
@@ -55,7 +61,6 @@ __device__ __forceinline__ float selu(float x) {
 __device__ __forceinline__ float selu_precise(float x) {
     return SELU_SCALE * (x > 0.0f ? x : SELU_ALPHA * expm1f(x));
 }
-constexpr int HBINS = 4096;        // score histogram bins (uniform in score, monotone)
 
 struct ALCtrl {
     int n_cand;       // candidates above threshold
@@ -81,19 +86,11 @@ __device__ __forceinline__ void al_split_weight(float v, _Float16& hi, _Float16&
     lo = (_Float16)((v - (float)hi) * sslam::SPLIT_SCALE);
 }
 
-struct Dims {
-    int H, W, C;          // input image
-    int h, w;             // resized
-    int Hp, Wp;           // padded (multiple of 32)
-    int pl, pt;           // left / top padding
-};
-
 // Batched extraction (sslam_aliked_extract_batch_dev): F frames of one size go through ONE launch sequence.  Every
 // per-frame buffer of frame f sits `fs` bytes behind frame 0's (one workspace block per frame, carved identically),
 // so a kernel takes frame 0's pointers plus that stride and finds its frame in a grid dimension; weights and the
 // blur taps are shared.  The arithmetic of a frame does not depend on F: a batch gives the single-frame results bit
-// for bit.
-constexpr int MAX_FRAMES = 16;
+// for bit.  (MAX_FRAMES: al_plan.hpp)
 template <typename T> __device__ __forceinline__ T* fsh(T* p, int f, size_t fs) {
     // byte arithmetic on the POINTER, and no null test: a round trip through an integer, or a phi with a null constant, loses
     // the global address space - every load behind it becomes a flat_load, which also counts against the LDS counter, so
@@ -267,7 +264,6 @@ __global__ void al_conv32_wfrag_kernel(const float* __restrict__ w /*[ci 32][tap
 //      throughout (3 x (27 + 3 + 54) v_mfma_f32_32x32x16_f16 per step).  Four independent waves per workgroup, every A fragment
 //      in registers: one workgroup per CU, no workgroup barrier after the affine tables are staged.
 // ------------------------------------------------------------------------ //
-constexpr int B2_SW = 30;                                   // output pixels per strip
 constexpr int B2_PXP = 24, B2_ROWP = 34 * B2_PXP, B2_PLP = 3 * B2_ROWP;          // pooled ring (halves)
 constexpr int B2_PXT = 40, B2_ROWT = 32 * B2_PXT, B2_PLT = 3 * B2_ROWT;          // t2 ring (halves)
 constexpr int B2_RING = 2 * B2_PLP + 2 * B2_PLT;                                   // halves per wave
@@ -460,7 +456,6 @@ __global__ __launch_bounds__(256, 1) void al_block2_rows_kernel(const float* __r
 //      32 pixels from x0 - 1, zero outside the map = conv2's padding).  Step y: prefetch image row y + 3; conv1 -> ring row
 //      y + 1; conv2 row y -> x1 (planar fp32).  Arithmetic per output as in al_conv16_rows_kernel<3, true> + al_conv16h_rows_kernel.
 // ------------------------------------------------------------------------ //
-constexpr int B1_SW = 30;
 __global__ __launch_bounds__(64) void al_block1_rows_kernel(const float* __restrict__ in /* image [3][H][W] */, float* __restrict__ out /* x1 [16][H][W] */,
                                                            int H, int W, int hs, const float* __restrict__ w1 /*[3][9][16]*/,
                                                            const float* __restrict__ a1, const float* __restrict__ b1,
@@ -1007,7 +1002,6 @@ __device__ __forceinline__ float up_eval(const float* __restrict__ p, const UpTa
 //     sum_c up(g_c)^2 = sum_{t, t'} w_t w_t' <g[t], g[t']> over the four taps = a quadratic form in S, H, V, D1, D2
 // (neighbours clamped at the border, where their tap weight is exactly zero).  One thread per level pixel, all three levels
 // of a frame in one launch; reads the planar levels.
-constexpr int AGG_PRE = 13;
 constexpr int PRE_UNROLL = 32;        // all 128 loads of a thread in flight at once: 5.4 us per frame (rounds of 8 / 16 channels: 11.3 / 18.5 - a memory latency per round)
 __global__ __launch_bounds__(256) void al_agg_pre_kernel(const float* __restrict__ g2cl /* planar [32][pixels] */, const float* __restrict__ g3cl,
                                                          const float* __restrict__ g4cl, const float* __restrict__ ws0 /*[128][8]*/,
@@ -1178,8 +1172,6 @@ __device__ __forceinline__ float2 feat_pair32(const Pyr& P, const float* __restr
 //  4. score head tail: 3x3 (8->4) SELU, 3x3 (4->4) SELU, 3x3 (4->1), sigmoid.
 //     One kernel, intermediate layers kept in LDS; zero padding at the padded-map border.
 // ------------------------------------------------------------------------ //
-constexpr int ST_W = 32, ST_H = 8;
-
 __global__ __launch_bounds__(256) void al_score_tail_kernel(const float* __restrict__ s8, int Hp, int Wp,
                                                             const float* __restrict__ w2 /*[8][9][4]*/,
                                                             const float* __restrict__ w4 /*[4][9][4]*/,
@@ -1252,8 +1244,6 @@ __global__ __launch_bounds__(256) void al_score_tail_kernel(const float* __restr
 // ------------------------------------------------------------------------ //
 //  5. DKD: simple_nms (5x5, two recovery rounds) + border + threshold -> candidates
 // ------------------------------------------------------------------------ //
-constexpr int NHALO = 10;     // dependency radius of simple_nms: 2 + 4 + 4
-
 // r04: NMS with a WAVE owning a tile and no LDS (the LDS-tile form it replaced: scripts/ubench/aliked_superseded_r04.hpp, al_nms_kernel): lane = column (64 of them, 44 + the 10-pixel halo either side), the
 // R rows of the column in registers.  A 5-wide row maximum is four DPP wave shifts fused into v_max (lanes shifted in from
 // outside the wave see themselves = an absent neighbour, as the LDS tile's rim was), a 5-tall column maximum three register
@@ -1262,7 +1252,6 @@ constexpr int NHALO = 10;     // dependency radius of simple_nms: 2 + 4 + 4
 // float map (r03 form: 3.7 x halo redundancy, ~60 LDS operations per element, 9.6 us per frame; max is exact and
 // associative, so the order of the pooling steps changes nothing: nms is bit-identical.  block_sum's partition changes, i.e.
 // the rounding of the mean score the no-candidate fallback thresholds on).
-constexpr int NW_R = 48, NW_OW = 64 - 2 * NHALO, NW_OH = NW_R - 2 * NHALO;
 static_assert(NW_R <= 64 && NW_OH > 0, "a column's rows are the bits of one 64-bit word");
 
 // lane i <- lane i - 1 / lane i + 1; the wave's first / last lane reads 0 (bound_ctrl): the identity of the mask ORs, and for the
@@ -1413,7 +1402,6 @@ __global__ __launch_bounds__(256) void al_nms_wave_kernel(const float* __restric
 // key = score_bits << 32 | (0xffffffff - index)  -> larger key = better (score desc, index asc)
 // (end of r04: launched for the mean-score fallback only - `fallback` = 1, returns at once when the NMS waves found candidates
 //  above the detection threshold; the detection-threshold pass itself is the tail of al_nms_wave_kernel)
-constexpr int COLLECT_PPT = 16;     // pixels per thread: 4096 per block -> ~80 blocks, one same-address atomic each
 
 __global__ __launch_bounds__(256) void al_collect_kernel(const float* __restrict__ nms, int n_px, float thr,
                                                          int fallback, const float* __restrict__ block_sum,
@@ -1497,7 +1485,6 @@ __global__ void al_reset_kernel(ALCtrl* __restrict__ ctrl, unsigned* __restrict_
 //     SET of keys (histogram cut + ordered edge bin); their ORDER is a rank count spread over the chip in
 //     al_refine_kernel (r03: a 66-pass bitonic sort of the 2048 keys in this one block was 30 of its 45 us).
 // ------------------------------------------------------------------------ //
-constexpr int SEL_CAP = 8192;      // max keypoints (sort capacity)
 
 __device__ void bitonic_sort_desc(unsigned long long* a, int n_pow2) {
     for (int k = 2; k <= n_pow2; k <<= 1)
@@ -1514,7 +1501,6 @@ __device__ void bitonic_sort_desc(unsigned long long* a, int n_pow2) {
         }
 }
 
-constexpr int EDGE_CAP = 2048;     // candidates allowed in the cut bin before falling back to radix select
 
 __global__ __launch_bounds__(1024) void al_select_kernel(const unsigned long long* __restrict__ cand, int cap,
                                                          int n_limit, unsigned long long* __restrict__ sel_keys,
@@ -1621,7 +1607,6 @@ __global__ __launch_bounds__(1024) void al_select_kernel(const unsigned long lon
 // ~index, so descending key order is score descending, index ascending - torch.topk's order / raster order), counted by
 // 8 lanes per key over 1/8 of the set each; then soft-argmax refinement + score sampling (DKD.forward sub_pixel=True)
 // by the first lane of each group, written at that position
-constexpr int REFINE_KPB = 32;       // keys per 256-thread block
 __global__ __launch_bounds__(256) void al_refine_kernel(const float* __restrict__ score, int h, int w,
                                                         const unsigned long long* __restrict__ sel_keys,
                                                         int* __restrict__ kp_index, float* __restrict__ kp_norm,
@@ -1724,7 +1709,6 @@ __global__ __launch_bounds__(256) void al_patch_kernel(Pyr P0, const float* __re
 }
 
 // offsets = clamp(conv1x1(selu(h32)) + b) ; sample positions in un-padded pixel coordinates
-constexpr int SDDH_KSPLIT = 4;
 
 __global__ void al_offsets_kernel(const float* __restrict__ h32 /*[KSPLIT][cap][32] partial pre-activations*/,
                                   int cap, const float* __restrict__ b1,
@@ -2017,6 +2001,7 @@ struct sslam_aliked {
     float *out_xy, *out_desc, *out_score;
     int32_t* out_n;
     Dims last{};
+    sslam::ALKptPlan kp{};            // the descriptor head's grids for max_kpts (fixed at creation)
     bool use_graphs = false;          // replay the per-call launch sequence as a cached hipGraph
     sslam::GraphCache graphs;
 };
@@ -2045,169 +2030,108 @@ int al_bind_weights(sslam_aliked* g, size_t n_floats) {
     return 0;
 }
 
-struct ResizePlan { int h, w, blur, ky, kx; float sy, sx; };
+constexpr int SEL_LDS = (SEL_CAP + EDGE_CAP) * 8;       // al_select_kernel: dynamic LDS bytes
 
-ResizePlan resize_plan(int H, int W, int resize) {
-    // kornia resize(side='long'): the long side becomes `resize`, the other int(resize / aspect)
-    ResizePlan p{};
-    const double ar = (double)W / (double)H;
-    if (ar > 1.0) { p.h = (int)(resize / ar); p.w = resize; }
-    else { p.h = resize; p.w = (int)(resize * ar); }
-    const double fy = (double)H / p.h, fx = (double)W / p.w;
-    p.blur = (fy > fx ? fy : fx) > 1.0;
-    p.sy = (float)((fy - 1.0) / 2.0 > 0.001 ? (fy - 1.0) / 2.0 : 0.001);
-    p.sx = (float)((fx - 1.0) / 2.0 > 0.001 ? (fx - 1.0) / 2.0 : 0.001);
-    const double ksy = 2.0 * 2 * ((fy - 1.0) / 2.0 > 0.001 ? (fy - 1.0) / 2.0 : 0.001);
-    const double ksx = 2.0 * 2 * ((fx - 1.0) / 2.0 > 0.001 ? (fx - 1.0) / 2.0 : 0.001);
-    p.ky = (int)(ksy > 3 ? ksy : 3); p.kx = (int)(ksx > 3 ? ksx : 3);
-    if (p.ky % 2 == 0) ++p.ky;
-    if (p.kx % 2 == 0) ++p.kx;
-    return p;
-}
-
-// network-size bookkeeping of one image (resize to 1024 on the long side, centred pad to a multiple of 32)
-Dims al_dims(int H, int W, int C) {
-    const ResizePlan rp = resize_plan(H, W, 1024);
-    Dims d{};
-    d.H = H; d.W = W; d.C = C; d.h = rp.h; d.w = rp.w;
-    const int pad_h = (((d.h / 32) + 1) * 32 - d.h) % 32, pad_w = (((d.w / 32) + 1) * 32 - d.w) % 32;
-    d.Hp = d.h + pad_h; d.Wp = d.w + pad_w; d.pl = pad_w / 2; d.pt = pad_h / 2;
-    return d;
-}
-
-// (host-side state such as g->last is set by the ENTRY POINTS, not here: a graph replay skips this function)
-// One launch sequence for F frames of one size: every grid carries the frame in its last used dimension and every
-// per-frame pointer is frame 0's plus f * g->fs (see fsh above).  F = 1 is the single-frame entry.
-int al_enqueue(sslam_aliked* g, int F, const FrameIn& srcs, int H, int W, int C, int n_limit, const FrameOut& outs) {
+// One launch sequence for p.F frames of one size: every grid carries the frame in its last used dimension and every
+// per-frame pointer is frame 0's plus f * g->fs (see fsh above).  F = 1 is the single-frame entry.  A list of launches: every
+// size, split and grid extent is a field of the call's plan or of the instance's keypoint plan (al_plan.hpp).
+// (The ENTRY POINTS set host-side state such as g->last and refuse a frame - al_admit: a graph replay skips this function, and
+// its first run is a stream capture.)
+int al_enqueue(sslam_aliked* g, const sslam::ALPlan& p, const FrameIn& srcs, int n_limit, const FrameOut& outs) {
     hipStream_t s = g->ctx->stream;
     (void)hipGetLastError();     // (a stale error of another library on this thread - e.g. RCCL's probes - is not ours)
-    const ResizePlan rp = resize_plan(H, W, 1024);
-    const Dims d = al_dims(H, W, C);
-    SSLAM_REQUIRE(d.Hp <= g->Hp_cap && d.Wp <= g->Wp_cap && d.h >= 8 && d.w >= 8,
-                  "sslam_aliked: network size %dx%d outside the instance capacity %dx%d", d.Hp, d.Wp,
-                  g->Hp_cap, g->Wp_cap);
-    SSLAM_REQUIRE(F >= 1 && F <= g->max_frames, "sslam_aliked: %d frames, instance capacity %d", F, g->max_frames);
-    const int Hp = d.Hp, Wp = d.Wp;
-    const unsigned uF = (unsigned)F;
+    const Dims& d = p.d;
+    const sslam::ALKptPlan& k = g->kp;
+    const int F = p.F, KF = p.KF, NK = k.NK;
     const size_t fs = g->fs;
-    SSLAM_REQUIRE(rp.kx <= 31 && rp.ky <= 31, "sslam_aliked: blur kernel too large (%d,%d)", rp.kx, rp.ky);
-    hipLaunchKernelGGL(al_reset_kernel, dim3(uF), dim3(256), 0, s, g->ctrl, g->hist, fs, g->gk, rp.kx, rp.sx, rp.ky, rp.sy);
+    const dim3 b256(256);
+    hipLaunchKernelGGL(al_reset_kernel, dim3(F), b256, 0, s, g->ctrl, g->hist, fs, g->gk, p.kx, p.sx, p.ky, p.sy);
 
-    hipLaunchKernelGGL(al_to_float_kernel, dim3(sslam::cdiv(W, 256), H, uF), dim3(256), 0, s, srcs, g->fsrc, d,
-                       g->gk, rp.kx, rp.blur, fs);
-    hipLaunchKernelGGL(al_resize_pad_kernel, dim3(sslam::cdiv(Wp, 256), Hp, uF), dim3(256), 0, s, g->fsrc, g->img, d,
-                       g->gk + 32, rp.ky, rp.blur, fs);
-    // block1 (conv1 + conv2 fused): ~3 waves per SIMD when the batch allows; at least four rows per wave (two extra conv1 rows per block:
-    // short blocks only when one or two frames have to fill the chip)
-    {
-        const int strips = sslam::cdiv(Wp, B1_SW);
-        const int nblk = std::max(1, std::min(sslam::cdiv(Hp, 4), 3072 / std::max(1, strips * F)));
-        const int hs1 = sslam::cdiv(Hp, nblk);
-        hipLaunchKernelGGL(al_block1_rows_kernel, dim3(strips, sslam::cdiv(Hp, hs1), uF), dim3(64), 0, s, g->img, g->x1, Hp, Wp, hs1,
-                           g->b1c1.w, g->b1c1.a, g->b1c1.b, g->b1c2f, g->b1c2.a, g->b1c2.b, g->ctrl, fs);
-    }
-    // block2 at 1/2 (pooling + conv1 + 1 x 1 branch + conv2 + residual fused): one wave per SIMD when the batch allows; at least
-    // three rows per wave (two extra t2 rows per block).  (A frame's values do not depend on these splits: no sum is re-associated.)
-    const int H2 = Hp / 2, W2 = Wp / 2;
-    {
-        const int strips = sslam::cdiv(W2, B2_SW);
-        const int nblk = std::max(1, std::min(sslam::cdiv(H2, 3), 1024 / std::max(1, strips * F)));
-        const int hs2 = sslam::cdiv(H2, nblk), nb = sslam::cdiv(H2, hs2), n_waves = strips * nb * F;
-        hipLaunchKernelGGL(al_block2_rows_kernel, dim3(sslam::cdiv(n_waves, 4)), dim3(256), B2_LDS, s, g->x1, g->x2, H2, W2, hs2, nb, strips, n_waves,
-                           g->b2c1f, g->b2c2f, g->b2c1.a, g->b2c1.b, g->b2db, g->b2c2.a, g->b2c2.b, g->ctrl, fs);
-    }
-    constexpr int DCN4_CS = 4;      // workgroups per pixel tile of the 1/32 deformable layers (output channels split: 10 tiles per frame there)
-    constexpr int DCN3_CS = 1;
+    hipLaunchKernelGGL(al_to_float_kernel, dim3(p.to_float_gx, d.H, F), b256, 0, s, srcs, g->fsrc, d, g->gk, p.kx, p.blur, fs);
+    hipLaunchKernelGGL(al_resize_pad_kernel, dim3(p.pad_gx, d.Hp, F), b256, 0, s, g->fsrc, g->img, d, g->gk + 32, p.ky, p.blur, fs);
+    // block1 (conv1 + conv2 fused), block2 at 1/2 (pooling + conv1 + 1 x 1 branch + conv2 + residual fused)
+    hipLaunchKernelGGL(al_block1_rows_kernel, dim3(p.b1_strips, p.b1_nb, F), dim3(64), 0, s, g->img, g->x1, d.Hp, d.Wp, p.b1_hs,
+                       g->b1c1.w, g->b1c1.a, g->b1c1.b, g->b1c2f, g->b1c2.a, g->b1c2.b, g->ctrl, fs);
+    hipLaunchKernelGGL(al_block2_rows_kernel, dim3(p.b2_gx), b256, B2_LDS, s, g->x1, g->x2, p.H2, p.W2, p.b2_hs, p.b2_nb, p.b2_strips,
+                       p.b2_waves, g->b2c1f, g->b2c2f, g->b2c1.a, g->b2c1.b, g->b2db, g->b2c2.a, g->b2c2.b, g->ctrl, fs);
     // block3 at 1/8 (deformable): per layer the offset conv, then sampling + contraction + BN (+ 1 x 1 residual branch) + SELU fused
-    const int H3 = Hp / 8, W3 = Wp / 8, HW3 = H3 * W3;
-    const dim3 g3(sslam::cdiv(W3, 32), H3, uF);
-    hipLaunchKernelGGL(al_avgpool_kernel, dim3(sslam::cdiv(32 * HW3, 256), uF), dim3(256), 0, s, g->x2, g->p3, 32, H2, W2, 4, fs, g->p3cl);
-    const float mo3 = (float)(H3 > W3 ? H3 : W3) / 4.0f;
-    hipLaunchKernelGGL((al_offset_conv_h_kernel<32>), g3, dim3(256), 0, s, g->p3cl, g->off, H3, W3, g->b3c1of, g->b3c1.ob, mo3, g->ctrl, fs);
-    hipLaunchKernelGGL((al_dcn_h_kernel<32, 64, 0, DCN3_CS>), dim3(DCN3_CS * sslam::cdiv(W3, 32), H3, uF), dim3(256), 0, s, g->p3cl, g->off, nullptr, H3, W3, g->b3c1f, g->b3c1.b, nullptr, g->t3, g->t3cl, g->ctrl, fs);
-    hipLaunchKernelGGL((al_offset_conv_h_kernel<64>), g3, dim3(256), 0, s, g->t3cl, g->off, H3, W3, g->b3c2of, g->b3c2.ob, mo3, g->ctrl, fs);
-    hipLaunchKernelGGL((al_dcn_h_kernel<64, 64, 32, DCN3_CS>), dim3(DCN3_CS * sslam::cdiv(W3, 32), H3, uF), dim3(256), 0, s, g->t3cl, g->off, g->p3cl, H3, W3, g->b3c2f, g->b3c2.b, g->b3db, g->x3, nullptr, g->ctrl, fs);
-    // block4 at 1/32
-    const int H4 = Hp / 32, W4 = Wp / 32, HW4 = H4 * W4;
-    const dim3 g4(sslam::cdiv(W4, 32), H4, uF);
+    const dim3 off3 = dim3(p.off3_gx, p.H3, F), dcn3 = dim3(p.dcn3_gx, p.H3, F);
+    hipLaunchKernelGGL(al_avgpool_kernel, dim3(p.pool3_gx, F), b256, 0, s, g->x2, g->p3, 32, p.H2, p.W2, 4, fs, g->p3cl);
+    hipLaunchKernelGGL((al_offset_conv_h_kernel<32>), off3, b256, 0, s, g->p3cl, g->off, p.H3, p.W3, g->b3c1of, g->b3c1.ob, p.mo3, g->ctrl, fs);
+    hipLaunchKernelGGL((al_dcn_h_kernel<32, 64, 0, DCN3_CS>), dcn3, b256, 0, s, g->p3cl, g->off, nullptr, p.H3, p.W3, g->b3c1f, g->b3c1.b, nullptr, g->t3, g->t3cl, g->ctrl, fs);
+    hipLaunchKernelGGL((al_offset_conv_h_kernel<64>), off3, b256, 0, s, g->t3cl, g->off, p.H3, p.W3, g->b3c2of, g->b3c2.ob, p.mo3, g->ctrl, fs);
+    hipLaunchKernelGGL((al_dcn_h_kernel<64, 64, 32, DCN3_CS>), dcn3, b256, 0, s, g->t3cl, g->off, g->p3cl, p.H3, p.W3, g->b3c2f, g->b3c2.b, g->b3db, g->x3, nullptr, g->ctrl, fs);
+    // block4 at 1/32: DCN4_CS workgroups per tile, 128 / DCN4_CS output channels each
+    const dim3 off4 = dim3(p.off4_gx, p.H4, F), dcn4 = dim3(p.dcn4_gx, p.H4, F);
     sslam::graph_cut(s);       // (pieces of 10 - 12 launches: a graph's replay stops for ~25 us after its 15th kernel node, common.hpp)
-    hipLaunchKernelGGL(al_avgpool_kernel, dim3(sslam::cdiv(64 * HW4, 256), uF), dim3(256), 0, s, g->x3, g->p4, 64, H3, W3, 4, fs, g->p4cl);
-    const float mo4 = (float)(H4 > W4 ? H4 : W4) / 4.0f;
-    hipLaunchKernelGGL((al_offset_conv_h_kernel<64>), g4, dim3(256), 0, s, g->p4cl, g->off, H4, W4, g->b4c1of, g->b4c1.ob, mo4, g->ctrl, fs);
-    const dim3 g4s(DCN4_CS * sslam::cdiv(W4, 32), H4, uF);  // DCN4_CS workgroups per tile, 128 / DCN4_CS output channels each
-    hipLaunchKernelGGL((al_dcn_h_kernel<64, 128, 0, DCN4_CS>), g4s, dim3(256), 0, s, g->p4cl, g->off, nullptr, H4, W4, g->b4c1f, g->b4c1.b, nullptr, g->t4, g->t4cl, g->ctrl, fs);
-    hipLaunchKernelGGL((al_offset_conv_h_kernel<128>), g4, dim3(256), 0, s, g->t4cl, g->off, H4, W4, g->b4c2of, g->b4c2.ob, mo4, g->ctrl, fs);
-    hipLaunchKernelGGL((al_dcn_h_kernel<128, 128, 64, DCN4_CS>), g4s, dim3(256), 0, s, g->t4cl, g->off, g->p4cl, H4, W4, g->b4c2f, g->b4c2.b, g->b4db, g->x4, nullptr, g->ctrl, fs);
+    hipLaunchKernelGGL(al_avgpool_kernel, dim3(p.pool4_gx, F), b256, 0, s, g->x3, g->p4, 64, p.H3, p.W3, 4, fs, g->p4cl);
+    hipLaunchKernelGGL((al_offset_conv_h_kernel<64>), off4, b256, 0, s, g->p4cl, g->off, p.H4, p.W4, g->b4c1of, g->b4c1.ob, p.mo4, g->ctrl, fs);
+    hipLaunchKernelGGL((al_dcn_h_kernel<64, 128, 0, DCN4_CS>), dcn4, b256, 0, s, g->p4cl, g->off, nullptr, p.H4, p.W4, g->b4c1f, g->b4c1.b, nullptr, g->t4, g->t4cl, g->ctrl, fs);
+    hipLaunchKernelGGL((al_offset_conv_h_kernel<128>), off4, b256, 0, s, g->t4cl, g->off, p.H4, p.W4, g->b4c2of, g->b4c2.ob, p.mo4, g->ctrl, fs);
+    hipLaunchKernelGGL((al_dcn_h_kernel<128, 128, 64, DCN4_CS>), dcn4, b256, 0, s, g->t4cl, g->off, g->p4cl, p.H4, p.W4, g->b4c2f, g->b4c2.b, g->b4db, g->x4, nullptr, g->ctrl, fs);
     // gates
-    hipLaunchKernelGGL(al_gate_kernel<32>, dim3(sslam::cdiv(H2 * W2, 256), uF), dim3(256), 0, s, g->x2, g->g2, H2 * W2, g->gw2, g->g2cl, fs);
-    {
-        const int ba = sslam::cdiv(32 * HW3, 256), bb = sslam::cdiv(32 * HW4, 256);
-        hipLaunchKernelGGL(al_gate_small_kernel, dim3(ba + bb, uF), dim3(256), 0, s, GateSmall{g->x3, g->g3, 64, HW3, g->gw3, g->g3cl},
-                           GateSmall{g->x4, g->g4, 128, HW4, g->gw4, g->g4cl}, ba, fs);
-    }
+    hipLaunchKernelGGL(al_gate_kernel<32>, dim3(p.gate2_gx, F), b256, 0, s, g->x2, g->g2, p.HW2, g->gw2, g->g2cl, fs);
+    hipLaunchKernelGGL(al_gate_small_kernel, dim3(p.gate34_gx, F), b256, 0, s, GateSmall{g->x3, g->g3, 64, p.HW3, g->gw3, g->g3cl},
+                       GateSmall{g->x4, g->g4, 128, p.HW4, g->gw4, g->g4cl}, p.gate3_gx, fs);
     // aggregation + score head
-    Pyr P{g->x1, g->g2, g->g3, g->g4, g->gw1, Hp, Wp, g->g1cl};
-    {
-        auto step = [](int full, int S) { return (float)(full / S - 1) / (float)(full - 1); };
-        P.sy2 = step(Hp, 2); P.sx2 = step(Wp, 2); P.sy8 = step(Hp, 8); P.sx8 = step(Wp, 8);
-        P.sy32 = step(Hp, 32); P.sx32 = step(Wp, 32);
-        P.g2cl = g->g2cl; P.g3cl = g->g3cl; P.g4cl = g->g4cl;
-        P.pre2 = g->pre2; P.pre3 = g->pre3; P.pre4 = g->pre4;
-    }
-    hipLaunchKernelGGL(al_agg_pre_kernel, dim3(sslam::cdiv(H2 * W2 + HW3 + HW4, 256), uF), dim3(256), 0, s, g->g2, g->g3, g->g4,
-                       g->sh0, g->pre2, g->pre3, g->pre4, Hp, Wp, fs);
-    hipLaunchKernelGGL(al_aggregate_kernel, dim3(sslam::cdiv(Wp, 256), Hp, uF), dim3(256), 0, s, P, g->sh0, g->s8, g->rnorm, fs);
-    hipLaunchKernelGGL(al_score_tail_kernel, dim3(sslam::cdiv(Wp, ST_W), sslam::cdiv(Hp, ST_H), uF), dim3(256), 0, s, g->s8,
-                       Hp, Wp, g->sh2, g->sh4, g->sh6, g->score, d.h, d.w, d.pl, d.pt, fs);
+    Pyr P{g->x1, g->g2, g->g3, g->g4, g->gw1, d.Hp, d.Wp, g->g1cl};
+    P.sy2 = p.sy2; P.sx2 = p.sx2; P.sy8 = p.sy8; P.sx8 = p.sx8; P.sy32 = p.sy32; P.sx32 = p.sx32;
+    P.g2cl = g->g2cl; P.g3cl = g->g3cl; P.g4cl = g->g4cl;
+    P.pre2 = g->pre2; P.pre3 = g->pre3; P.pre4 = g->pre4;
+    hipLaunchKernelGGL(al_agg_pre_kernel, dim3(p.agg_pre_gx, F), b256, 0, s, g->g2, g->g3, g->g4, g->sh0, g->pre2, g->pre3, g->pre4,
+                       d.Hp, d.Wp, fs);
+    hipLaunchKernelGGL(al_aggregate_kernel, dim3(p.pad_gx, d.Hp, F), b256, 0, s, P, g->sh0, g->s8, g->rnorm, fs);
+    hipLaunchKernelGGL(al_score_tail_kernel, dim3(p.tail_gx, p.tail_gy, F), b256, 0, s, g->s8, d.Hp, d.Wp, g->sh2, g->sh4, g->sh6,
+                       g->score, d.h, d.w, d.pl, d.pt, fs);
     // DKD
-    const int nbx = sslam::cdiv(d.w, NW_OW), nby = sslam::cdiv(d.h, NW_OH), npx = d.h * d.w;
-    hipLaunchKernelGGL(al_nms_wave_kernel, dim3(sslam::cdiv(nbx * nby, 4), uF), dim3(256), 0, s, g->score, d.h, d.w, nbx, nbx * nby,
-                       g->nms, g->bsum, 0.2f, g->cand, g->cand_cap, g->ctrl, g->hist, fs);
+    hipLaunchKernelGGL(al_nms_wave_kernel, dim3(p.nms_gx, F), b256, 0, s, g->score, d.h, d.w, p.nbx, p.n_tiles, g->nms, g->bsum, 0.2f,
+                       g->cand, g->cand_cap, g->ctrl, g->hist, fs);
     sslam::graph_cut(s);
-    hipLaunchKernelGGL(al_collect_kernel, dim3(sslam::cdiv(npx, 256 * COLLECT_PPT), uF), dim3(256), 0, s, g->nms, npx, 0.0f, 1, g->bsum,
-                       nbx * nby, g->cand, g->cand_cap, g->ctrl, g->hist, fs);
-    hipLaunchKernelGGL(al_select_kernel, dim3(uF), dim3(1024), (SEL_CAP + EDGE_CAP) * 8, s, g->cand, g->cand_cap, n_limit,
-                       g->sel_keys, g->ctrl, g->hist, fs);
-    const int NK = g->max_kpts;
-    hipLaunchKernelGGL(al_refine_kernel, dim3(sslam::cdiv(NK, REFINE_KPB), uF), dim3(256), 0, s, g->score, d.h, d.w, g->sel_keys,
-                       g->kp_index, g->kp_norm, g->kp_score, g->ctrl, fs);
+    hipLaunchKernelGGL(al_collect_kernel, dim3(p.collect_gx, F), b256, 0, s, g->nms, p.npx, 0.0f, 1, g->bsum, p.n_tiles, g->cand,
+                       g->cand_cap, g->ctrl, g->hist, fs);
+    hipLaunchKernelGGL(al_select_kernel, dim3(F), dim3(1024), SEL_LDS, s, g->cand, g->cand_cap, n_limit, g->sel_keys, g->ctrl, g->hist, fs);
+    hipLaunchKernelGGL(al_refine_kernel, dim3(k.refine_gx, F), b256, 0, s, g->score, d.h, d.w, g->sel_keys, g->kp_index, g->kp_norm,
+                       g->kp_score, g->ctrl, fs);
     // SDDH
-    hipLaunchKernelGGL(al_patch_kernel, dim3(sslam::cdiv(NK * 3, 4), uF), dim3(256), 0, s, P, g->rnorm, d.pl, d.pt, d.h, d.w,
-                       g->kp_norm, g->patch, g->ctrl, fs);
-    hipLaunchKernelGGL((al_gemm_kernel<64, 64, 1, 1>), dim3(1, sslam::cdiv(NK, 64), SDDH_KSPLIT * uF), dim3(256), 0, s, g->patch,
-                       1152, g->d_ow, nullptr, 32, g->h32, 1, NK, 0, g->ctrl, SDDH_KSPLIT, fs);
-    const float mo = (float)(d.h > d.w ? d.h : d.w) / 4.0f;
-    hipLaunchKernelGGL(al_offsets_kernel, dim3(sslam::cdiv(NK * 32, 256), uF), dim3(256), 0, s, g->h32, NK, g->d_ob, g->d_w2, g->d_b2,
-                       g->kp_norm, d.h, d.w, mo, g->pos, g->ctrl, fs);
+    hipLaunchKernelGGL(al_patch_kernel, dim3(k.patch_gx, F), b256, 0, s, P, g->rnorm, d.pl, d.pt, d.h, d.w, g->kp_norm, g->patch, g->ctrl, fs);
+    hipLaunchKernelGGL((al_gemm_kernel<64, 64, 1, 1>), dim3(1, k.rows64, KF), b256, 0, s, g->patch, 1152, g->d_ow, nullptr, 32, g->h32,
+                       1, NK, 0, g->ctrl, SDDH_KSPLIT, fs);
+    hipLaunchKernelGGL(al_offsets_kernel, dim3(k.offsets_gx, F), b256, 0, s, g->h32, NK, g->d_ob, g->d_w2, g->d_b2, g->kp_norm, d.h, d.w,
+                       p.mo, g->pos, g->ctrl, fs);
     // (r04: `sampled` and `feats` hold the (hi, lo) fp16 planes of [rows][128] - the same bytes as the fp32 rows they replaced)
-    const size_t plane = (size_t)(NK * 16 + 64) * 128;
     _Float16* sampled_h = reinterpret_cast<_Float16*>(g->sampled);
     _Float16* feats_h = reinterpret_cast<_Float16*>(g->feats);
-    hipLaunchKernelGGL(al_sample_kernel, dim3(sslam::cdiv(NK * 16, 4), uF), dim3(256), 0, s, P, g->rnorm, d.pl, d.pt, d.h,
-                       d.w, g->pos, sampled_h, plane, g->ctrl, fs);
-    hipLaunchKernelGGL((al_gemm_h_kernel<64, 128, 1, 2, true>), dim3(1, sslam::cdiv(NK * 16, 64), uF), dim3(256), 0, s, sampled_h, plane,
-                       128, g->d_sf_s, (size_t)128 * 128, 128, nullptr, feats_h, plane, 16, NK * 16, g->ctrl, 1, fs);
-    // (batches: 64 x 128 tiles - the 16.8 MB of sampled-feature planes are read once; with two column blocks the PMC counters showed
-    //  35.7 MB fetched per frame.  One or two frames: 64 x 64 tiles, twice the workgroups.  Same k-split, same order: bit-identical)
-    if (F >= 4)
-        hipLaunchKernelGGL((al_gemm_h_kernel<64, 128, 1, 2, false>), dim3(1, sslam::cdiv(NK, 64), SDDH_KSPLIT * uF), dim3(256), 0, s, feats_h,
-                           plane, 2048, g->d_agg_s, (size_t)128 * 2048, 128, g->raw, nullptr, 0, 1, NK, g->ctrl, SDDH_KSPLIT, fs);
+    hipLaunchKernelGGL(al_sample_kernel, dim3(k.sample_gx, F), b256, 0, s, P, g->rnorm, d.pl, d.pt, d.h, d.w, g->pos, sampled_h,
+                       k.plane, g->ctrl, fs);
+    hipLaunchKernelGGL((al_gemm_h_kernel<64, 128, 1, 2, true>), dim3(1, k.rows64_x16, F), b256, 0, s, sampled_h, k.plane, 128, g->d_sf_s,
+                       (size_t)128 * 128, 128, nullptr, feats_h, k.plane, 16, k.rows_x16, g->ctrl, 1, fs);
+    if (p.agg_tile == sslam::ALAggTile::T64x128)
+        hipLaunchKernelGGL((al_gemm_h_kernel<64, 128, 1, 2, false>), dim3(1, k.rows64, KF), b256, 0, s, feats_h, k.plane, 2048,
+                           g->d_agg_s, (size_t)128 * 2048, 128, g->raw, nullptr, 0, 1, NK, g->ctrl, SDDH_KSPLIT, fs);
     else
-        hipLaunchKernelGGL((al_gemm_h_kernel<64, 64, 1, 1, false>), dim3(2, sslam::cdiv(NK, 64), SDDH_KSPLIT * uF), dim3(256), 0, s, feats_h,
-                           plane, 2048, g->d_agg_s, (size_t)128 * 2048, 128, g->raw, nullptr, 0, 1, NK, g->ctrl, SDDH_KSPLIT, fs);
-    const float scale_x = (float)d.w / (float)W, scale_y = (float)d.h / (float)H;
-    hipLaunchKernelGGL(al_finalize_kernel, dim3(sslam::cdiv(NK, 4), uF), dim3(256), 0, s, g->raw, NK, g->kp_norm, g->kp_score,
-                       d.h, d.w, scale_x, scale_y, outs, g->ctrl, g->range_sticky, fs);
+        hipLaunchKernelGGL((al_gemm_h_kernel<64, 64, 1, 1, false>), dim3(2, k.rows64, KF), b256, 0, s, feats_h, k.plane, 2048,
+                           g->d_agg_s, (size_t)128 * 2048, 128, g->raw, nullptr, 0, 1, NK, g->ctrl, SDDH_KSPLIT, fs);
+    hipLaunchKernelGGL(al_finalize_kernel, dim3(k.finalize_gx, F), b256, 0, s, g->raw, NK, g->kp_norm, g->kp_score, d.h, d.w,
+                       p.scale_x, p.scale_y, outs, g->ctrl, g->range_sticky, fs);
     SSLAM_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
-// single-frame form
-int al_enqueue(sslam_aliked* g, const uint8_t* img_dev, int H, int W, int C, int n_limit, float* xy_out,
-               float* desc_out, float* score_out, int32_t* n_out) {
-    FrameIn in{}; FrameOut out{};
-    in.img[0] = img_dev; out.xy[0] = xy_out; out.desc[0] = desc_out; out.score[0] = score_out; out.n[0] = n_out;
-    return al_enqueue(g, 1, in, H, W, C, n_limit, out);
+// the single-frame entries: a batch of one
+struct Frames { FrameIn in{}; FrameOut out{}; };
+Frames al_one_frame(const uint8_t* img_dev, float* xy_out, float* desc_out, float* score_out, int32_t* n_out) {
+    Frames f;
+    f.in.img[0] = img_dev; f.out.xy[0] = xy_out; f.out.desc[0] = desc_out; f.out.score[0] = score_out; f.out.n[0] = n_out;
+    return f;
+}
+
+// Records the call's bookkeeping (also of a frame that is then refused: sslam_aliked_debug_read 2 reports it) and refuses what
+// the instance cannot take - before anything is launched or captured.
+int al_admit(sslam_aliked* g, const sslam::ALPlan& p) {
+    g->last = p.d;
+    char why[160];
+    SSLAM_REQUIRE(sslam::al_refusal(p, g->Hp_cap, g->Wp_cap, g->max_frames, why, sizeof(why)) == sslam::ALRefusal::None, "%s", why);
+    return 0;
 }
 
 }  // namespace
@@ -2226,10 +2150,11 @@ int sslam_aliked_create_batched(sslam_ctx* ctx, const float* weights, size_t n_f
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     sslam_aliked* g = new sslam_aliked();
     g->ctx = ctx; g->max_h = max_h; g->max_w = max_w; g->max_kpts = max_kpts; g->max_frames = max_frames;
-    // the network never runs larger than 1024 on the long side (+ padding to /32)
-    g->Hp_cap = 1024 + 32; g->Wp_cap = 1024 + 32;
-    const size_t HWp = (size_t)g->Hp_cap * g->Wp_cap, HWi = (size_t)max_h * max_w, NK = (size_t)max_kpts;
-    g->cand_cap = (int)(1024 * 1024);
+    g->kp = sslam::al_kpt_plan(max_kpts);
+    // the network never runs larger than AL_LONG_SIDE on the long side (+ padding to a multiple of AL_PAD_DIV)
+    g->Hp_cap = sslam::AL_LONG_SIDE + sslam::AL_PAD_DIV; g->Wp_cap = sslam::AL_LONG_SIDE + sslam::AL_PAD_DIV;
+    const sslam::ALExtents e = sslam::al_extents((size_t)g->Hp_cap * g->Wp_cap, (size_t)max_h * max_w, (size_t)max_kpts);
+    g->cand_cap = sslam::CAND_CAP;
     // shared by all frames: weights, their re-ordered copies, the blur taps
     auto carve_shared = [&](sslam::Arena& A) {
         g->blob = A.take<float>(n_floats);
@@ -2245,28 +2170,28 @@ int sslam_aliked_create_batched(sslam_ctx* ctx, const float* weights, size_t n_f
     };
     // one workspace block per frame of a batch (frame f's copy of a buffer = frame 0's + f * g->fs bytes)
     auto carve_frame = [&](sslam::Arena& A) {
-        g->ctrl = A.take<ALCtrl>(1);
-        g->in_u8 = A.take<uint8_t>(HWi * 4);
-        g->fsrc = A.take<float>(3 * HWi); g->img = A.take<float>(3 * HWp);
-        g->x1 = A.take<float>(16 * HWp); g->x2 = A.take<float>(32 * HWp / 4);
-        g->p3 = A.take<float>(32 * HWp / 64); g->off = A.take<float>(18 * HWp / 64);
-        g->t3 = A.take<float>(64 * HWp / 64); g->x3 = A.take<float>(64 * HWp / 64);
-        g->p3cl = A.take<float>(32 * HWp / 64); g->t3cl = A.take<float>(64 * HWp / 64);
-        g->p4cl = A.take<float>(64 * HWp / 1024); g->t4cl = A.take<float>(128 * HWp / 1024);
-        g->p4 = A.take<float>(64 * HWp / 1024); g->t4 = A.take<float>(128 * HWp / 1024); g->x4 = A.take<float>(128 * HWp / 1024);
-        g->g2 = A.take<float>(32 * HWp / 4); g->g3 = A.take<float>(32 * HWp / 64); g->g4 = A.take<float>(32 * HWp / 1024);
-        g->g2cl = A.take<float>(32 * HWp / 4); g->g3cl = A.take<float>(32 * HWp / 64); g->g4cl = A.take<float>(32 * HWp / 1024);
-        g->s8 = A.take<float>(8 * HWp); g->rnorm = A.take<float>(HWp); g->g1cl = A.take<float>(32 * HWp);
-        g->pre2 = A.take<float>(AGG_PRE * HWp / 4); g->pre3 = A.take<float>(AGG_PRE * HWp / 64); g->pre4 = A.take<float>(AGG_PRE * HWp / 1024);
-        g->score = A.take<float>(HWp); g->nms = A.take<float>(HWp); g->bsum = A.take<float>(4096);
-        g->cand = A.take<unsigned long long>(g->cand_cap); g->hist = A.take<unsigned>(HBINS);
-        g->kp_index = A.take<int>(SEL_CAP); g->sel_keys = A.take<unsigned long long>(SEL_CAP);
-        g->kp_norm = A.take<float>(2 * NK + 64); g->kp_score = A.take<float>(NK + 64);
-        g->patch = A.take<float>((NK + 64) * 1152); g->h32 = A.take<float>(SDDH_KSPLIT * (NK + 64) * 32); g->pos = A.take<float>(NK * 32 + 64);
-        g->sampled = A.take<float>((NK * 16 + 64) * 128); g->feats = A.take<float>((NK * 16 + 64) * 128);
-        g->raw = A.take<float>(SDDH_KSPLIT * (NK + 64) * 128);
-        g->out_xy = A.take<float>(2 * NK); g->out_desc = A.take<float>(NK * 128); g->out_score = A.take<float>(NK);
-        g->out_n = A.take<int32_t>(16);
+        g->ctrl = A.take<ALCtrl>(e.ctrl);
+        g->in_u8 = A.take<uint8_t>(e.in_u8);
+        g->fsrc = A.take<float>(e.fsrc); g->img = A.take<float>(e.img);
+        g->x1 = A.take<float>(e.x1); g->x2 = A.take<float>(e.x2);
+        g->p3 = A.take<float>(e.p3); g->off = A.take<float>(e.off);
+        g->t3 = A.take<float>(e.t3); g->x3 = A.take<float>(e.x3);
+        g->p3cl = A.take<float>(e.p3cl); g->t3cl = A.take<float>(e.t3cl);
+        g->p4cl = A.take<float>(e.p4cl); g->t4cl = A.take<float>(e.t4cl);
+        g->p4 = A.take<float>(e.p4); g->t4 = A.take<float>(e.t4); g->x4 = A.take<float>(e.x4);
+        g->g2 = A.take<float>(e.g2); g->g3 = A.take<float>(e.g3); g->g4 = A.take<float>(e.g4);
+        g->g2cl = A.take<float>(e.g2cl); g->g3cl = A.take<float>(e.g3cl); g->g4cl = A.take<float>(e.g4cl);
+        g->s8 = A.take<float>(e.s8); g->rnorm = A.take<float>(e.rnorm); g->g1cl = A.take<float>(e.g1cl);
+        g->pre2 = A.take<float>(e.pre2); g->pre3 = A.take<float>(e.pre3); g->pre4 = A.take<float>(e.pre4);
+        g->score = A.take<float>(e.score); g->nms = A.take<float>(e.nms); g->bsum = A.take<float>(e.bsum);
+        g->cand = A.take<unsigned long long>(e.cand); g->hist = A.take<unsigned>(e.hist);
+        g->kp_index = A.take<int>(e.kp_index); g->sel_keys = A.take<unsigned long long>(e.sel_keys);
+        g->kp_norm = A.take<float>(e.kp_norm); g->kp_score = A.take<float>(e.kp_score);
+        g->patch = A.take<float>(e.patch); g->h32 = A.take<float>(e.h32); g->pos = A.take<float>(e.pos);
+        g->sampled = A.take<float>(e.sampled); g->feats = A.take<float>(e.feats);
+        g->raw = A.take<float>(e.raw);
+        g->out_xy = A.take<float>(e.out_xy); g->out_desc = A.take<float>(e.out_desc); g->out_score = A.take<float>(e.out_score);
+        g->out_n = A.take<int32_t>(e.out_n);
     };
     sslam::Arena probe;
     probe.measure();
@@ -2311,8 +2236,7 @@ int sslam_aliked_create_batched(sslam_ctx* ctx, const float* weights, size_t n_f
         }
     }
     SSLAM_HIP_CHECK(hipFuncSetAttribute((const void*)al_block2_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)B2_LDS));
-    SSLAM_HIP_CHECK(hipFuncSetAttribute((const void*)al_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (SEL_CAP + EDGE_CAP) * 8));
+    SSLAM_HIP_CHECK(hipFuncSetAttribute((const void*)al_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SEL_LDS));
     sslam::ctx_retain(ctx);
     *out = g;
     return 0;
@@ -2347,12 +2271,14 @@ int sslam_aliked_extract_dev(sslam_aliked* g, const uint8_t* img, int H, int W, 
                              float* desc_out, float* score_out, int32_t* n_out) {
     SSLAM_REQUIRE(g && img && xy_out && desc_out && n_out, "sslam_aliked_extract_dev: NULL argument");
     if (int rc = al_check_image(g, H, W, C, max_kpts)) return rc;
-    g->last = al_dims(H, W, C);
-    if (!g->use_graphs) return al_enqueue(g, img, H, W, C, max_kpts, xy_out, desc_out, score_out, n_out);
+    const sslam::ALPlan plan = sslam::al_plan(H, W, C, 1);
+    if (int rc = al_admit(g, plan)) return rc;
+    const Frames f = al_one_frame(img, xy_out, desc_out, score_out, n_out);
+    if (!g->use_graphs) return al_enqueue(g, plan, f.in, max_kpts, f.out);
     const std::vector<uint64_t> key{(uint64_t)img, (uint64_t)H, (uint64_t)W, (uint64_t)C, (uint64_t)max_kpts,
                                     (uint64_t)xy_out, (uint64_t)desc_out, (uint64_t)score_out, (uint64_t)n_out};
     return sslam::run_cached(g->graphs, g->ctx->stream, key,
-                             [&] { return al_enqueue(g, img, H, W, C, max_kpts, xy_out, desc_out, score_out, n_out); });
+                             [&] { return al_enqueue(g, plan, f.in, max_kpts, f.out); });
 }
 
 int sslam_aliked_extract_batch_dev(sslam_aliked* g, int n_frames, const uint8_t* const* imgs, int H, int W, int C,
@@ -2371,14 +2297,12 @@ int sslam_aliked_extract_batch_dev(sslam_aliked* g, int n_frames, const uint8_t*
         key.push_back((uint64_t)imgs[f]); key.push_back((uint64_t)xy_out[f]); key.push_back((uint64_t)desc_out[f]);
         key.push_back((uint64_t)out.score[f]); key.push_back((uint64_t)n_out[f]);
     }
-    g->last = al_dims(H, W, C);
-    if (!g->use_graphs) return al_enqueue(g, n_frames, in, H, W, C, max_kpts, out);
-    return sslam::run_cached(g->graphs, g->ctx->stream, key, [&] { return al_enqueue(g, n_frames, in, H, W, C, max_kpts, out); });
+    const sslam::ALPlan plan = sslam::al_plan(H, W, C, n_frames);
+    if (int rc = al_admit(g, plan)) return rc;
+    if (!g->use_graphs) return al_enqueue(g, plan, in, max_kpts, out);
+    return sslam::run_cached(g->graphs, g->ctx->stream, key, [&] { return al_enqueue(g, plan, in, max_kpts, out); });
 }
 
-/* Replay the launch sequence of sslam_aliked_extract_dev as a cached hipGraph (one graph per
- * distinct argument tuple, LRU of 128): for callers that cycle through a fixed set of buffers,
- * as the frame pipeline does.  Results are identical; only the host cost of a call changes. */
 int sslam_aliked_range_overflow(sslam_aliked* g, int* flag_out) {
     SSLAM_REQUIRE(g && flag_out, "sslam_aliked_range_overflow: NULL argument");
     hipStream_t s = g->ctx->stream;
@@ -2393,6 +2317,9 @@ int sslam_aliked_range_overflow(sslam_aliked* g, int* flag_out) {
     return 0;
 }
 
+/* Replay the launch sequence of sslam_aliked_extract_dev as a cached hipGraph (one graph per
+ * distinct argument tuple, LRU of 128): for callers that cycle through a fixed set of buffers,
+ * as the frame pipeline does.  Results are identical; only the host cost of a call changes. */
 int sslam_aliked_use_graphs(sslam_aliked* g, int enable) {
     SSLAM_REQUIRE(g != nullptr, "sslam_aliked_use_graphs: NULL instance");
     if (!enable) { (void)hipStreamSynchronize(g->ctx->stream); g->graphs.clear(); }
@@ -2404,11 +2331,13 @@ int sslam_aliked_extract_host(sslam_aliked* g, const uint8_t* img, int H, int W,
                               float* desc_out, float* score_out, int32_t* n_out) {
     SSLAM_REQUIRE(g && img && xy_out && desc_out && n_out, "sslam_aliked_extract_host: NULL argument");
     if (int rc = al_check_image(g, H, W, C, max_kpts)) return rc;
+    const sslam::ALPlan plan = sslam::al_plan(H, W, C, 1);
+    if (int rc = al_admit(g, plan)) return rc;
     SSLAM_HIP_CHECK(hipSetDevice(g->ctx->device));
     hipStream_t s = g->ctx->stream;
     SSLAM_HIP_CHECK(hipMemcpyAsync(g->in_u8, img, (size_t)H * W * C, hipMemcpyHostToDevice, s));
-    g->last = al_dims(H, W, C);
-    if (int rc = al_enqueue(g, g->in_u8, H, W, C, max_kpts, g->out_xy, g->out_desc, g->out_score, g->out_n)) return rc;
+    const Frames f = al_one_frame(g->in_u8, g->out_xy, g->out_desc, g->out_score, g->out_n);
+    if (int rc = al_enqueue(g, plan, f.in, max_kpts, f.out)) return rc;
     int32_t n = 0;
     SSLAM_HIP_CHECK(hipMemcpyAsync(&n, g->out_n, 4, hipMemcpyDeviceToHost, s));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
@@ -2437,12 +2366,13 @@ int sslam_aliked_debug_read(sslam_aliked* g, int which, void* dst, size_t bytes)
     SSLAM_REQUIRE(g && dst, "sslam_aliked_debug_read: NULL argument");
     SSLAM_HIP_CHECK(hipStreamSynchronize(g->ctx->stream));
     const Dims& d = g->last;
-    const size_t HWp = (size_t)d.Hp * d.Wp;
+    // elements the LAST frame filled of every buffer (the instance carved the same counts at its capacities)
+    const sslam::ALExtents e = sslam::al_extents((size_t)d.Hp * d.Wp, (size_t)d.H * d.W, (size_t)g->max_kpts);
     const void* src = nullptr; size_t cap = 0;
     int32_t dims[8];
     switch (which) {
         case 0: src = g->score; cap = (size_t)d.h * d.w * 4; break;
-        case 1: src = g->kp_index; cap = (size_t)SEL_CAP * 4; break;
+        case 1: src = g->kp_index; cap = e.kp_index * 4; break;
         case 2: {
             ALCtrl c;
             SSLAM_HIP_CHECK(hipMemcpy(&c, g->ctrl, sizeof(c), hipMemcpyDeviceToHost));
@@ -2452,22 +2382,22 @@ int sslam_aliked_debug_read(sslam_aliked* g, int which, void* dst, size_t bytes)
             memcpy(dst, dims, bytes);
             return 0;
         }
-        case 3: src = g->x1; cap = 16 * HWp * 4; break;
-        case 4: src = g->x2; cap = 32 * HWp / 4 * 4; break;
-        case 5: src = g->x3; cap = 64 * HWp / 64 * 4; break;
-        case 6: src = g->x4; cap = 128 * HWp / 1024 * 4; break;
-        case 7: src = g->img; cap = 3 * HWp * 4; break;
+        case 3: src = g->x1; cap = e.x1 * 4; break;
+        case 4: src = g->x2; cap = e.x2 * 4; break;
+        case 5: src = g->x3; cap = e.x3 * 4; break;
+        case 6: src = g->x4; cap = e.x4 * 4; break;
+        case 7: src = g->img; cap = e.img * 4; break;
         case 8: src = g->nms; cap = (size_t)d.h * d.w * 4; break;
         case 9: src = g->kp_norm; cap = (size_t)g->max_kpts * 8; break;
-        case 10: src = g->g1cl; cap = 32 * HWp * 4; break;           // (r04: the aggregation's outputs and the gated levels, for determinism checks)
-        case 11: src = g->rnorm; cap = HWp * 4; break;
-        case 12: src = g->g2; cap = 32 * HWp / 4 * 4; break;
-        case 13: src = g->g3; cap = 32 * HWp / 64 * 4; break;
-        case 14: src = g->g4; cap = 32 * HWp / 1024 * 4; break;
-        case 15: src = g->pre2; cap = AGG_PRE * HWp / 4 * 4; break;
-        case 16: src = g->pre3; cap = AGG_PRE * HWp / 64 * 4; break;
-        case 17: src = g->pre4; cap = AGG_PRE * HWp / 1024 * 4; break;
-        case 18: src = g->s8; cap = 8 * HWp * 4; break;
+        case 10: src = g->g1cl; cap = e.g1cl * 4; break;           // (r04: the aggregation's outputs and the gated levels, for determinism checks)
+        case 11: src = g->rnorm; cap = e.rnorm * 4; break;
+        case 12: src = g->g2; cap = e.g2 * 4; break;
+        case 13: src = g->g3; cap = e.g3 * 4; break;
+        case 14: src = g->g4; cap = e.g4 * 4; break;
+        case 15: src = g->pre2; cap = e.pre2 * 4; break;
+        case 16: src = g->pre3; cap = e.pre3 * 4; break;
+        case 17: src = g->pre4; cap = e.pre4 * 4; break;
+        case 18: src = g->s8; cap = e.s8 * 4; break;
         case 19: src = g->pos; cap = (size_t)g->max_kpts * 32 * 4; break;      // SDDH sample positions [n][16][2], un-padded pixels (x, y)
         case 20: src = g->patch; cap = (size_t)g->max_kpts * 1152 * 4; break;  // SDDH 3 x 3 patches [n][c * 9 + tap]
         default: SSLAM_REQUIRE(false, "sslam_aliked_debug_read: unknown buffer %d", which);

@@ -293,3 +293,42 @@ def test_batch_of_five_thin_frames_equals_the_single_frame_entry(gpu_ctx, h, w):
     for p in dev + xy + de + sc + nn:
         gpu_ctx.free(p)
     al.close()
+
+
+def test_refused_frame_in_front_of_a_graph_capture(gpu_ctx, native):
+    """With use_graphs on, a call that is not cached yet captures its launch sequence: the 16 x 2064 frame (network 7 x 1024) must
+    be refused BEFORE that capture begins.  The instance then captures the 16 x 2048 frame and gives the keypoints, descriptors
+    and scores of plain launches on a fresh instance bit for bit, and the second call - a replay - gives them again."""
+    sd = load_pkg("weights").random_aliked_state_dict(0)
+    AL = load_pkg("aliked").AlikedHIP
+    K = MAX_KPTS
+    dev = gpu_ctx.upload(frames.noise_frame(0, h=16, w=2048))
+    bad = gpu_ctx.upload(frames.noise_frame(1, h=16, w=2064))
+    xy, de, sc, nn = gpu_ctx.malloc(K * 8), gpu_ctx.malloc(K * 512), gpu_ctx.malloc(K * 4), gpu_ctx.malloc(16)
+
+    def call(al, ptr, w):
+        for p, nbytes in ((xy, K * 8), (de, K * 512), (sc, K * 4), (nn, 16)):
+            gpu_ctx.memset_async(p, 0xff, nbytes)
+        al.extract_dev(ptr, 16, w, 3, xy, de, sc, nn, K)
+        gpu_ctx.sync()
+        n = np.empty(1, np.int32); gpu_ctx.d2h(n, nn)
+        a = np.empty((K, 2), np.float32); d = np.empty((K, 128), np.float32); s = np.empty(K, np.float32)
+        gpu_ctx.d2h(a, xy); gpu_ctx.d2h(d, de); gpu_ctx.d2h(s, sc)
+        k = int(n[0])
+        return a[:k], d[:k], s[:k]
+
+    plain = AL(sd, max_num_keypoints=K, max_h=16, max_w=2064, ctx=gpu_ctx)
+    want = call(plain, dev, 2048)
+    plain.close()
+    assert 50 < len(want[0]) < K
+    al = AL(sd, max_num_keypoints=K, max_h=16, max_w=2064, ctx=gpu_ctx)
+    al.use_graphs(True)
+    with pytest.raises(native.NativeError, match="network size 32x1024 outside"):
+        call(al, bad, 2064)
+    assert (_dims(al)["h"], _dims(al)["w"]) == (7, 1024)
+    for _ in range(2):                                   # capture + launch, then a replay
+        for x, y in zip(call(al, dev, 2048), want):
+            np.testing.assert_array_equal(x, y)
+    al.close()
+    for p in (dev, bad, xy, de, sc, nn):
+        gpu_ctx.free(p)
