@@ -108,6 +108,24 @@ int launch_ba(sslam_ctx* ctx, int n_obs, const int32_t* pose_idx, const int32_t*
     return 0;
 }
 
+// the slab's pieces of one host call
+struct BAPieces {
+    int32_t* pose_idx; int32_t* point_idx;    // [n_obs]
+    double* uv;                               // [n_obs][2]
+    double* q; double* t;                     // [n_poses][4], [n_poses][3]
+    double* X;                                // [n_points][3]
+    double* intr;                             // [4]
+    double* r;                                // [n_obs][2]
+    double* Jq; double* Jt; double* JX;       // [n_obs][8], [n_obs][6], [n_obs][6]
+};
+
+void ba_bind(sslam::Slab& sl, BAPieces& p, size_t N, size_t n_poses, size_t n_points) {
+    p.pose_idx = sl.take<int32_t>(N); p.point_idx = sl.take<int32_t>(N); p.uv = sl.take<double>(N * 2);
+    p.q = sl.take<double>(n_poses * 4); p.t = sl.take<double>(n_poses * 3); p.X = sl.take<double>(n_points * 3);
+    p.intr = sl.take<double>(4); p.r = sl.take<double>(N * 2);
+    p.Jq = sl.take<double>(N * 8); p.Jt = sl.take<double>(N * 6); p.JX = sl.take<double>(N * 6);
+}
+
 }  // namespace
 
 extern "C" {
@@ -147,33 +165,25 @@ int sslam_ba_residual_jacobian_host(sslam_ctx* ctx, int n_obs, const int32_t* po
     }
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t N = (size_t)n_obs;
-    sslam::Carver carve;
-    const size_t o_pi = carve(N * 4), o_xi = carve(N * 4), o_uv = carve(N * 16);
-    const size_t o_q = carve((size_t)n_poses * 32), o_t = carve((size_t)n_poses * 24);
-    const size_t o_X = carve((size_t)n_points * 24), o_in = carve(32);
-    const size_t o_r = carve(N * 16), o_Jq = carve(N * 64), o_Jt = carve(N * 48), o_JX = carve(N * 48);
-    char* b;
-    if (int rc = sslam::ctx_scratch(ctx, carve.bytes, &b)) return rc;
+    BAPieces p{};
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { ba_bind(sl, p, N, (size_t)n_poses, (size_t)n_points); })) return rc;
     hipStream_t s = ctx->stream;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + o_pi, pose_idx, N * 4, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + o_xi, point_idx, N * 4, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + o_uv, uv, N * 16, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + o_q, q, (size_t)n_poses * 32, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + o_t, t, (size_t)n_poses * 24, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + o_X, X, (size_t)n_points * 24, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + o_in, intr, 32, hipMemcpyHostToDevice, s));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, p.pose_idx, pose_idx, N));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, p.point_idx, point_idx, N));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, p.uv, uv, N * 2));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, p.q, q, (size_t)n_poses * 4));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, p.t, t, (size_t)n_poses * 3));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, p.X, X, (size_t)n_points * 3));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, p.intr, intr, 4));
     const bool jac = Jq != nullptr;
-    int rc = launch_ba(ctx, n_obs, (const int32_t*)(b + o_pi), (const int32_t*)(b + o_xi),
-                       (const double*)(b + o_uv), (const double*)(b + o_q), (const double*)(b + o_t),
-                       (const double*)(b + o_X), (const double*)(b + o_in), (double*)(b + o_r),
-                       jac ? (double*)(b + o_Jq) : nullptr, jac ? (double*)(b + o_Jt) : nullptr,
-                       jac ? (double*)(b + o_JX) : nullptr);
+    int rc = launch_ba(ctx, n_obs, p.pose_idx, p.point_idx, p.uv, p.q, p.t, p.X, p.intr, p.r, jac ? p.Jq : nullptr,
+                       jac ? p.Jt : nullptr, jac ? p.JX : nullptr);
     if (rc) return rc;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(r, b + o_r, N * 16, hipMemcpyDeviceToHost, s));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, r, p.r, N * 2));
     if (jac) {
-        SSLAM_HIP_CHECK(hipMemcpyAsync(Jq, b + o_Jq, N * 64, hipMemcpyDeviceToHost, s));
-        SSLAM_HIP_CHECK(hipMemcpyAsync(Jt, b + o_Jt, N * 48, hipMemcpyDeviceToHost, s));
-        SSLAM_HIP_CHECK(hipMemcpyAsync(JX, b + o_JX, N * 48, hipMemcpyDeviceToHost, s));
+        SSLAM_HIP_CHECK(sslam::copy_down(s, Jq, p.Jq, N * 8));
+        SSLAM_HIP_CHECK(sslam::copy_down(s, Jt, p.Jt, N * 6));
+        SSLAM_HIP_CHECK(sslam::copy_down(s, JX, p.JX, N * 6));
     }
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
     return 0;

@@ -552,6 +552,27 @@ __global__ __launch_bounds__(LM_T) void lm_decide_kernel(LMArgs a) {
     }
 }
 
+// the slab-backed pointers of LMArgs, in slab order; sized by a's counts.  n_ps: observations of optimised poses (ps_obs)
+void lm_bind(sslam::Slab& sl, LMArgs& a, size_t n_ps, bool big) {
+    const size_t N = (size_t)a.n_obs, P = (size_t)a.P, Q = (size_t)a.Q, Po = (size_t)a.Po, m = 6 * Po;
+    a.obs_pose = sl.take<int32_t>(N); a.obs_point = sl.take<int32_t>(N); a.obs_slot = sl.take<int32_t>(N);
+    a.uv = sl.take<double>(N * 2);
+    a.pt_ptr = sl.take<int32_t>(Q + 1); a.pt_obs = sl.take<int32_t>(N);
+    a.ps_ptr = sl.take<int32_t>(Po + 1); a.ps_obs = sl.take<int32_t>(n_ps);
+    a.slot_pose = sl.take<int32_t>(Po); a.pose_slot = sl.take<int32_t>(P); a.intr = sl.take<double>(4);
+    a.q[0] = sl.take<double>(P * 4); a.q[1] = sl.take<double>(P * 4); a.t[0] = sl.take<double>(P * 3);
+    a.t[1] = sl.take<double>(P * 3); a.X[0] = sl.take<double>(Q * 3); a.X[1] = sl.take<double>(Q * 3);
+    a.rw = sl.take<double>(N * 2); a.JXw = sl.take<double>(N * 6); a.Jpw = sl.take<double>(N * 12);
+    a.V = sl.take<double>(Q * 6); a.gX = sl.take<double>(Q * 3); a.Vinv = sl.take<double>(Q * 6);
+    a.Wd = sl.take<double>(Po * Q * 18); a.Y = sl.take<double>(Po * Q * 18);
+    a.U = sl.take<double>(Po * 36); a.gP = sl.take<double>(Po * 6);
+    a.S = sl.take<double>(m * m); a.rhs = sl.take<double>(m); a.dP = sl.take<double>(m); a.dX = sl.take<double>(Q * 3);
+    a.Lbig = sl.take<double>(big ? m * m : 0);
+    a.pc = sl.take<double>((size_t)a.nb_obs); a.pm = sl.take<double>((size_t)a.nb_obs); a.pbad = sl.take<int>((size_t)a.nb_obs);
+    a.pstep = sl.take<double>((size_t)a.nb_pt); a.px = sl.take<double>((size_t)a.nb_pt); a.pgmax = sl.take<double>((size_t)a.nb_pt);
+    a.ctrl = sl.take<LMCtrl>(1);
+}
+
 }  // namespace
 
 extern "C" int sslam_ba_solve_host(sslam_ctx* ctx, int n_obs, const int32_t* pose_idx, const int32_t* point_idx,
@@ -595,58 +616,25 @@ extern "C" int sslam_ba_solve_host(sslam_ctx* ctx, int n_obs, const int32_t* pos
     }
 
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t N = (size_t)n_obs, P = (size_t)n_poses, Q = (size_t)n_points, m = 6 * (size_t)Po;
+    const size_t N = (size_t)n_obs, P = (size_t)n_poses, Q = (size_t)n_points;
     const int nb_obs = sslam::cdiv(n_obs, LM_T), nb_pt = sslam::cdiv(n_points, LM_T);
-    sslam::Carver carve;
-    const size_t o_pi = carve(N * 4), o_xi = carve(N * 4), o_sl = carve(N * 4), o_uv = carve(N * 16);
-    const size_t o_pp = carve((Q + 1) * 4), o_po = carve(N * 4), o_sp = carve((Po + 1) * 4), o_so = carve(ps_obs.size() * 4);
-    const size_t o_slp = carve((size_t)Po * 4), o_psl = carve(P * 4), o_in = carve(32);
-    const size_t o_q0 = carve(P * 32), o_q1 = carve(P * 32), o_t0 = carve(P * 24), o_t1 = carve(P * 24);
-    const size_t o_X0 = carve(Q * 24), o_X1 = carve(Q * 24);
-    const size_t o_rw = carve(N * 16), o_JX = carve(N * 48), o_Jp = carve(N * 96);
-    const size_t o_V = carve(Q * 48), o_gX = carve(Q * 24), o_Vi = carve(Q * 48);
-    const size_t o_Wd = carve((size_t)Po * Q * 144), o_Y = carve((size_t)Po * Q * 144);
-    const size_t o_U = carve((size_t)Po * 288), o_gP = carve((size_t)Po * 48);
-    const size_t o_S = carve(m * m * 8), o_rhs = carve(m * 8), o_dP = carve(m * 8), o_dX = carve(Q * 24);
     const bool big = Po > MAX_PO;
-    const size_t o_Lb = carve(big ? m * m * 8 : 0);
-    const size_t o_pc = carve((size_t)nb_obs * 8), o_pm = carve((size_t)nb_obs * 8), o_pb = carve((size_t)nb_obs * 4);
-    const size_t o_ps = carve((size_t)nb_pt * 8), o_px = carve((size_t)nb_pt * 8), o_pg = carve((size_t)nb_pt * 8);
-    const size_t o_ctrl = carve(sizeof(LMCtrl));
-    char* b;
-    if (int rc = sslam::ctx_scratch(ctx, carve.bytes, &b)) return rc;
-    hipStream_t s = ctx->stream;
-    auto up = [&](size_t o, const void* src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(b + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    SSLAM_HIP_CHECK(up(o_pi, pose_idx, N * 4)); SSLAM_HIP_CHECK(up(o_xi, point_idx, N * 4));
-    SSLAM_HIP_CHECK(up(o_sl, obs_slot.data(), N * 4)); SSLAM_HIP_CHECK(up(o_uv, uv, N * 16));
-    SSLAM_HIP_CHECK(up(o_pp, pt_ptr.data(), (Q + 1) * 4)); SSLAM_HIP_CHECK(up(o_po, pt_obs.data(), N * 4));
-    SSLAM_HIP_CHECK(up(o_sp, ps_ptr.data(), (Po + 1) * 4)); SSLAM_HIP_CHECK(up(o_so, ps_obs.data(), ps_obs.size() * 4));
-    SSLAM_HIP_CHECK(up(o_slp, slot_pose.data(), (size_t)Po * 4)); SSLAM_HIP_CHECK(up(o_psl, pose_slot.data(), P * 4));
-    SSLAM_HIP_CHECK(up(o_in, intr, 32));
-    SSLAM_HIP_CHECK(up(o_q0, q, P * 32)); SSLAM_HIP_CHECK(up(o_t0, t, P * 24)); SSLAM_HIP_CHECK(up(o_X0, X, Q * 24));
-    SSLAM_HIP_CHECK(hipMemsetAsync(b + o_ctrl, 0, sizeof(LMCtrl), s));
-
     LMArgs a{};
     a.n_obs = n_obs; a.P = n_poses; a.Q = n_points; a.Po = Po; a.points_const = points_const ? 1 : 0;
     a.nb_obs = nb_obs; a.nb_pt = nb_pt; a.delta = huber_delta;
-    a.obs_pose = (const int32_t*)(b + o_pi); a.obs_point = (const int32_t*)(b + o_xi); a.obs_slot = (const int32_t*)(b + o_sl);
-    a.uv = (const double*)(b + o_uv);
-    a.pt_ptr = (const int32_t*)(b + o_pp); a.pt_obs = (const int32_t*)(b + o_po);
-    a.ps_ptr = (const int32_t*)(b + o_sp); a.ps_obs = (const int32_t*)(b + o_so);
-    a.slot_pose = (const int32_t*)(b + o_slp); a.pose_slot = (const int32_t*)(b + o_psl);
-    a.intr = (const double*)(b + o_in);
-    a.q[0] = (double*)(b + o_q0); a.q[1] = (double*)(b + o_q1); a.t[0] = (double*)(b + o_t0); a.t[1] = (double*)(b + o_t1);
-    a.X[0] = (double*)(b + o_X0); a.X[1] = (double*)(b + o_X1);
-    a.rw = (double*)(b + o_rw); a.JXw = (double*)(b + o_JX); a.Jpw = (double*)(b + o_Jp);
-    a.V = (double*)(b + o_V); a.gX = (double*)(b + o_gX); a.Vinv = (double*)(b + o_Vi);
-    a.Wd = (double*)(b + o_Wd); a.Y = (double*)(b + o_Y); a.U = (double*)(b + o_U); a.gP = (double*)(b + o_gP);
-    a.Lbig = (double*)(b + o_Lb);
-    a.S = (double*)(b + o_S); a.rhs = (double*)(b + o_rhs); a.dP = (double*)(b + o_dP); a.dX = (double*)(b + o_dX);
-    a.pc = (double*)(b + o_pc); a.pm = (double*)(b + o_pm); a.pbad = (int*)(b + o_pb);
-    a.pstep = (double*)(b + o_ps); a.px = (double*)(b + o_px); a.pgmax = (double*)(b + o_pg);
-    a.ctrl = (LMCtrl*)(b + o_ctrl);
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { lm_bind(sl, a, ps_obs.size(), big); })) return rc;
+    hipStream_t s = ctx->stream;
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.obs_pose, pose_idx, N)); SSLAM_HIP_CHECK(sslam::copy_up(s, a.obs_point, point_idx, N));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.obs_slot, obs_slot.data(), N)); SSLAM_HIP_CHECK(sslam::copy_up(s, a.uv, uv, N * 2));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.pt_ptr, pt_ptr.data(), Q + 1)); SSLAM_HIP_CHECK(sslam::copy_up(s, a.pt_obs, pt_obs.data(), N));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.ps_ptr, ps_ptr.data(), (size_t)Po + 1));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.ps_obs, ps_obs.data(), ps_obs.size()));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.slot_pose, slot_pose.data(), (size_t)Po));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.pose_slot, pose_slot.data(), P));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.intr, intr, 4));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.q[0], q, P * 4)); SSLAM_HIP_CHECK(sslam::copy_up(s, a.t[0], t, P * 3));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.X[0], X, Q * 3));
+    SSLAM_HIP_CHECK(hipMemsetAsync(a.ctrl, 0, sizeof(LMCtrl), s));
 
     (void)hipGetLastError();     // (a stale error of another library on this thread is not ours)
     hipLaunchKernelGGL(lm_eval_kernel<false>, dim3(nb_obs), dim3(LM_T), 0, s, a);
@@ -667,12 +655,12 @@ extern "C" int sslam_ba_solve_host(sslam_ctx* ctx, int n_obs, const int32_t* pos
     }
     SSLAM_HIP_CHECK(hipGetLastError());
     LMCtrl h{};
-    SSLAM_HIP_CHECK(hipMemcpyAsync(&h, b + o_ctrl, sizeof(LMCtrl), hipMemcpyDeviceToHost, s));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, &h, a.ctrl, 1));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    const size_t oq = h.cur ? o_q1 : o_q0, ot = h.cur ? o_t1 : o_t0, oX = h.cur ? o_X1 : o_X0;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(q, b + oq, P * 32, hipMemcpyDeviceToHost, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(t, b + ot, P * 24, hipMemcpyDeviceToHost, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(X, b + oX, Q * 24, hipMemcpyDeviceToHost, s));
+    const int cur = h.cur ? 1 : 0;
+    SSLAM_HIP_CHECK(sslam::copy_down(s, q, a.q[cur], P * 4));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, t, a.t[cur], P * 3));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, X, a.X[cur], Q * 3));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
     summary[0] = h.iterations; summary[1] = h.successful; summary[2] = h.initial_cost; summary[3] = h.cost;
     summary[4] = h.done;       // 0 = max iterations reached

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/sslam_hip.h"
+#include "geom_slab.hpp"
 
 namespace sslam {
 
@@ -35,11 +36,9 @@ void set_error(const char* fmt, ...);
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// Carves one scratch slab into pieces: carve(n) places the next n bytes on a 256-byte boundary, at least 8 guard bytes
-// past the piece before, and returns their offset; `bytes` is the slab size so far.
-struct Carver {
-    size_t bytes = 0;
-    size_t operator()(size_t n) { const size_t o = bytes; bytes = align_up(bytes + n + 8, 256); return o; }
+// Slab's placement rule as byte offsets, for the KLT and undistort instances, which lay out slabs of their own.
+struct Carver : Slab {
+    size_t operator()(size_t n) { const size_t o = bytes; take<char>(n); return o; }
 };
 
 // Bump allocator over one hipMalloc'd slab: every instance sizes its workspace
@@ -206,4 +205,24 @@ void ctx_release(sslam_ctx* ctx);      // frees a closed context when its last i
 // *base = the context's scratch slab, grown to `bytes` first when it is smaller.  Growing drains the context's stream
 // (work enqueued earlier may still use the old slab) and reallocates: a pipeline sizes it once, with its largest problem.
 int ctx_scratch(sslam_ctx* ctx, size_t bytes, char** base);
+
+// The slab step of a geometry entry: `bind(Slab&)` measures, the context's slab grows to that, `bind` runs again on it.
+template <typename Bind>
+int ctx_bind(sslam_ctx* ctx, Bind&& bind) {
+    Slab m, s;
+    bind(m);
+    if (int rc = ctx_scratch(ctx, m.bytes, &s.base)) return rc;
+    bind(s);
+    return 0;
+}
+
+// Typed copies on a stream, `count` elements: host -> slab piece (none: no call), slab piece -> host.
+template <typename T>
+hipError_t copy_up(hipStream_t s, const T* piece, const T* host, size_t count) {
+    return count ? hipMemcpyAsync(const_cast<T*>(piece), host, count * sizeof(T), hipMemcpyHostToDevice, s) : hipSuccess;
+}
+template <typename T>
+hipError_t copy_down(hipStream_t s, T* host, const T* piece, size_t count) {
+    return hipMemcpyAsync(host, piece, count * sizeof(T), hipMemcpyDeviceToHost, s);
+}
 }

@@ -531,15 +531,11 @@ __global__ __launch_bounds__(EM_TAIL_T) void em_tail_kernel(EMArgs a) {
     if (threadIdx.x == 0) c->best_count = good;
 }
 
-struct EMScratch { size_t p1, p2, xn, sub, mod, nm, cnt, mask, ctrl, total; };
-EMScratch em_layout(size_t N, size_t H) {
-    EMScratch L{};
-    sslam::Carver carve;
-    L.p1 = carve(N * 8); L.p2 = carve(N * 8); L.xn = carve(N * 32); L.sub = carve(H * EM_MP * 4);
-    L.mod = carve(H * EM_MAXM * 9 * 8); L.nm = carve(H * 4); L.cnt = carve(H * EM_MAXM * 4); L.mask = carve(N);
-    L.ctrl = carve(sizeof(EMCtrl));
-    L.total = carve.bytes;
-    return L;
+// the slab-backed pointers of EMArgs, in slab order
+void em_bind(sslam::Slab& sl, EMArgs& a, size_t N, size_t H) {
+    a.p1 = sl.take<float>(N * 2); a.p2 = sl.take<float>(N * 2); a.xn = sl.take<double>(N * 4);
+    a.subsets = sl.take<int>(H * EM_MP); a.models = sl.take<double>(H * EM_MAXM * 9); a.nmodels = sl.take<int>(H);
+    a.counts = sl.take<int>(H * EM_MAXM); a.mask = sl.take<unsigned char>(N); a.ctrl = sl.take<EMCtrl>(1);
 }
 
 }  // namespace
@@ -560,23 +556,16 @@ extern "C" int sslam_essential_ransac_host(sslam_ctx* ctx, int n, const float* p
     if (direct) max_iters = 1;
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t N = (size_t)n;
-    const EMScratch L = em_layout(N, (size_t)max_iters);
-    char* b;
-    if (int rc = sslam::ctx_scratch(ctx, L.total, &b)) return rc;
-    hipStream_t s = ctx->stream;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.p1, pts1, N * 8, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.p2, pts2, N * 8, hipMemcpyHostToDevice, s));
     EMArgs a{};
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { em_bind(sl, a, N, (size_t)max_iters); })) return rc;
+    hipStream_t s = ctx->stream;
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.p1, pts1, N * 2));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.p2, pts2, N * 2));
     a.n = n; a.max_iters = max_iters; a.direct = direct; a.prob = prob;
     a.fx = K9[0]; a.fy = K9[4]; a.cx = K9[2]; a.cy = K9[5];
     const double th = thresh / ((a.fx + a.fy) / 2);
     a.t = (float)(th * th);
-    a.p1 = (const float*)(b + L.p1); a.p2 = (const float*)(b + L.p2); a.xn = (double*)(b + L.xn);
-    a.subsets = (int*)(b + L.sub); a.models = (double*)(b + L.mod); a.nmodels = (int*)(b + L.nm);
-    a.counts = (int*)(b + L.cnt); a.mask = (unsigned char*)(b + L.mask); a.ctrl = (EMCtrl*)(b + L.ctrl);
-    // the sample loop in chunks, as the other RANSAC entries have it: a chunk whose first sample lies beyond the (shrinking)
-    // budget is two early-exit launches; the result does not depend on the bounds
-    const int bounds[] = {0, std::min(8, max_iters), std::min(128, max_iters), max_iters};
+    const auto bounds = sslam::ransac_chunk_bounds(max_iters, 128);     // (the schedule: geom_slab.hpp)
     (void)hipGetLastError();     // (a stale error of another library on this thread is not ours)
     a.h0 = bounds[0]; a.h1 = bounds[1];
     hipLaunchKernelGGL(em_normalize_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
@@ -589,8 +578,8 @@ extern "C" int sslam_essential_ransac_host(sslam_ctx* ctx, int n, const float* p
     hipLaunchKernelGGL(em_tail_kernel, dim3(1), dim3(EM_TAIL_T), 0, s, a);       // (a.h0, a.h1: the last chunk)
     SSLAM_HIP_CHECK(hipGetLastError());
     EMCtrl h{};
-    SSLAM_HIP_CHECK(hipMemcpyAsync(&h, b + L.ctrl, sizeof(EMCtrl), hipMemcpyDeviceToHost, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(mask_out, b + L.mask, N, hipMemcpyDeviceToHost, s));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, &h, a.ctrl, 1));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, mask_out, a.mask, N));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
     if (E_out) for (int i = 0; i < EM_MAXM * 9; ++i) E_out[i] = h.best_h >= 0 ? h.E[i] : 0.0;
     if (info_out) {

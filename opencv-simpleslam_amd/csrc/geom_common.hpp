@@ -1,5 +1,6 @@
 // geom_common.hpp - device helpers shared by the geometry kernels (ransac_kernels.hip, homography_kernels.hip,
-// pnp_kernels.hip, ba_lm.hip).
+// essential_kernels.hip, pnp_kernels.hip, triangulate_kernels.hip, relative_pose_kernels.hip, ba_lm.hip).  Their host side
+// - the scratch slab's layout and the RANSAC chunk bounds - is geom_slab.hpp.
 //
 // The RANSAC pieces restate OpenCV 4.x's classic ptsetreg.cpp; both RANSAC files must stay bit-exact with the numpy
 // restatements under oracle/, so they share one copy.  Nothing here holds a contractible multiply-add: pnp_kernels.hip

@@ -529,14 +529,11 @@ __global__ __launch_bounds__(HG_TAIL_T) void hg_tail_kernel(HGArgs a) {
     }
 }
 
-struct HGScratch { size_t p1, p2, sub, mod, nm, cnt, mask, inl, ctrl, total; };
-HGScratch hg_layout(size_t N, size_t H) {
-    HGScratch L{};
-    sslam::Carver carve;
-    L.p1 = carve(N * 8); L.p2 = carve(N * 8); L.sub = carve(H * HG_MP * 4); L.mod = carve(H * 9 * 8);
-    L.nm = carve(H * 4); L.cnt = carve(H * 4); L.mask = carve(N); L.inl = carve(N * 4); L.ctrl = carve(sizeof(HGCtrl));
-    L.total = carve.bytes;
-    return L;
+// the slab-backed pointers of HGArgs, in slab order
+void hg_bind(sslam::Slab& sl, HGArgs& a, size_t N, size_t H) {
+    a.p1 = sl.take<float>(N * 2); a.p2 = sl.take<float>(N * 2); a.subsets = sl.take<int>(H * HG_MP);
+    a.models = sl.take<double>(H * 9); a.nmodels = sl.take<int>(H); a.counts = sl.take<int>(H);
+    a.mask = sl.take<unsigned char>(N); a.inl = sl.take<int>(N); a.ctrl = sl.take<HGCtrl>(1);
 }
 
 }  // namespace
@@ -557,21 +554,13 @@ extern "C" int sslam_homography_ransac_host(sslam_ctx* ctx, int n, const float* 
     if (direct) max_iters = 1;
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t N = (size_t)n;
-    const HGScratch L = hg_layout(N, (size_t)max_iters);
-    char* b;
-    if (int rc = sslam::ctx_scratch(ctx, L.total, &b)) return rc;
-    hipStream_t s = ctx->stream;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.p1, pts1, N * 8, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.p2, pts2, N * 8, hipMemcpyHostToDevice, s));
     HGArgs a{};
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { hg_bind(sl, a, N, (size_t)max_iters); })) return rc;
+    hipStream_t s = ctx->stream;
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.p1, pts1, N * 2));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.p2, pts2, N * 2));
     a.n = n; a.max_iters = max_iters; a.direct = direct; a.thresh = thresh; a.confidence = confidence;
-    a.p1 = (const float*)(b + L.p1); a.p2 = (const float*)(b + L.p2);
-    a.subsets = (int*)(b + L.sub); a.models = (double*)(b + L.mod); a.nmodels = (int*)(b + L.nm);
-    a.counts = (int*)(b + L.cnt); a.mask = (unsigned char*)(b + L.mask); a.inl = (int*)(b + L.inl);
-    a.ctrl = (HGCtrl*)(b + L.ctrl);
-    // the sample loop in chunks, as the F-matrix filter has it: a chunk whose first sample lies beyond the (shrinking) budget is
-    // two early-exit launches; the result does not depend on the bounds
-    const int bounds[] = {0, std::min(8, max_iters), std::min(128, max_iters), max_iters};
+    const auto bounds = sslam::ransac_chunk_bounds(max_iters, 128);     // (the schedule: geom_slab.hpp)
     (void)hipGetLastError();     // (a stale error of another library on this thread is not ours)
     a.h0 = bounds[0]; a.h1 = bounds[1];
     hipLaunchKernelGGL(hg_head_kernel, dim3(1), dim3(64), 0, s, a);
@@ -583,8 +572,8 @@ extern "C" int sslam_homography_ransac_host(sslam_ctx* ctx, int n, const float* 
     hipLaunchKernelGGL(hg_tail_kernel, dim3(1), dim3(HG_TAIL_T), 0, s, a);       // (a.h0, a.h1: the last chunk)
     SSLAM_HIP_CHECK(hipGetLastError());
     HGCtrl h{};
-    SSLAM_HIP_CHECK(hipMemcpyAsync(&h, b + L.ctrl, sizeof(HGCtrl), hipMemcpyDeviceToHost, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(mask_out, b + L.mask, N, hipMemcpyDeviceToHost, s));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, &h, a.ctrl, 1));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, mask_out, a.mask, N));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
     if (H_out) for (int i = 0; i < 9; ++i) H_out[i] = h.best_h >= 0 ? h.H[i] : 0.0;
     if (info_out) {

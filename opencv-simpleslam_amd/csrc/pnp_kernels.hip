@@ -865,8 +865,7 @@ __global__ __launch_bounds__(PN_LM_T) void pn_lm_kernel(PNArgs a) {
 // tail, LM.  A chunk whose first sample lies beyond the (shrinking) budget is an early-exit launch; the result does not
 // depend on the chunking.
 void pn_enqueue(hipStream_t s, PNArgs a) {
-    const int mi = a.max_iters;
-    const int bounds[] = {0, std::min(8, mi), std::min(64, mi), mi};
+    const auto bounds = sslam::ransac_chunk_bounds(a.max_iters, 64);     // (the schedule: geom_slab.hpp)
     (void)hipGetLastError();     // (a stale error of another library on this thread is not ours)
     {
         PNArgs h = a; h.h0 = bounds[0]; h.h1 = bounds[1];
@@ -883,37 +882,29 @@ void pn_enqueue(hipStream_t s, PNArgs a) {
     hipLaunchKernelGGL(pn_lm_kernel, dim3(1), dim3(PN_LM_T), lds, s, a);
 }
 
-struct PNScratch { size_t p3, p2, sub, mod, cnt, mask, start, T, info, n, ctrl, total; };
-PNScratch pn_layout(size_t N, size_t H) {
-    PNScratch L{};
-    sslam::Carver carve;
-    L.p3 = carve(N * 12); L.p2 = carve(N * 8); L.sub = carve(H * PN_MP * 4); L.mod = carve(H * 48);
-    L.cnt = carve(H * 4); L.mask = carve(N); L.start = carve(48); L.T = carve(128); L.info = carve(16); L.n = carve(4);
-    L.ctrl = carve(sizeof(PNCtrl));
-    L.total = carve.bytes;
-    return L;
+// the slab-backed pointers of PNArgs, in slab order
+void pn_bind(sslam::Slab& sl, PNArgs& a, size_t N, size_t H) {
+    a.p3 = sl.take<float>(N * 3); a.p2 = sl.take<float>(N * 2); a.subsets = sl.take<int>(H * PN_MP);
+    a.models = sl.take<double>(H * 6); a.counts = sl.take<int>(H); a.mask = sl.take<unsigned char>(N);
+    a.lm_start = sl.take<double>(6); a.Tcw_out = sl.take<double>(16); a.info_out = sl.take<int32_t>(4);
+    a.n_out = sl.take<int32_t>(1); a.ctrl = sl.take<PNCtrl>(1);
 }
 
 int pn_args(sslam_ctx* ctx, int n_max, const double* K9, int use_guess, double reproj_px, double confidence,
-            int max_iters, PNArgs& a, PNScratch& L, char*& b) {
+            int max_iters, PNArgs& a) {
     SSLAM_REQUIRE(K9 != nullptr, "PnP: K9 is NULL");
     SSLAM_REQUIRE(max_iters >= 0 && max_iters <= PN_MAX_ITERS, "PnP: max_iters %d outside [0, %d]", max_iters, PN_MAX_ITERS);
     SSLAM_REQUIRE(confidence > 0 && confidence < 1, "PnP: confidence %g outside (0, 1)", confidence);
     max_iters = std::max(max_iters, 1);
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
-    L = pn_layout((size_t)std::max(n_max, 1), (size_t)max_iters);
-    if (int rc = sslam::ctx_scratch(ctx, L.total, &b)) return rc;
     a = PNArgs{};
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { pn_bind(sl, a, (size_t)std::max(n_max, 1), (size_t)max_iters); }))
+        return rc;
     a.n_max = n_max; a.max_iters = max_iters; a.use_guess = use_guess;
     a.fx = K9[0]; a.fy = K9[4]; a.cx = K9[2]; a.cy = K9[5];
     a.confidence = confidence;
     const double px = (double)(float)reproj_px;            // solvePnPRansac's `float reprojectionError`
     a.thresh2 = (float)(px * px);
-    a.p3 = (float*)(b + L.p3); a.p2 = (float*)(b + L.p2);
-    a.subsets = (int*)(b + L.sub); a.models = (double*)(b + L.mod); a.counts = (int*)(b + L.cnt);
-    a.mask = (unsigned char*)(b + L.mask); a.lm_start = (double*)(b + L.start);
-    a.Tcw_out = (double*)(b + L.T); a.info_out = (int32_t*)(b + L.info); a.n_out = (int32_t*)(b + L.n);
-    a.ctrl = (PNCtrl*)(b + L.ctrl);
     return 0;
 }
 
@@ -927,8 +918,8 @@ extern "C" int sslam_pnp_ransac_dev(sslam_ctx* ctx, int n_points, const int32_t*
     SSLAM_REQUIRE(n_points >= 1, "sslam_pnp_ransac_dev: n_points %d < 1", n_points);
     SSLAM_REQUIRE(kp_of_point_dev && pts3d_dev && kp_xy_dev && Tcw_out_dev && info_out_dev,
                   "sslam_pnp_ransac_dev: NULL argument");
-    PNArgs a; PNScratch L; char* b;
-    if (int rc = pn_args(ctx, n_points, K9, Tcw_init16 != nullptr, reproj_px, confidence, max_iters, a, L, b)) return rc;
+    PNArgs a;
+    if (int rc = pn_args(ctx, n_points, K9, Tcw_init16 != nullptr, reproj_px, confidence, max_iters, a)) return rc;
     a.kp_of_point = kp_of_point_dev; a.map_xyz = pts3d_dev; a.kp_xy = kp_xy_dev;
     if (mask_out_dev) a.mask = mask_out_dev;
     a.Tcw_out = Tcw_out_dev; a.info_out = info_out_dev;
@@ -944,17 +935,17 @@ extern "C" int sslam_pnp_ransac_host(sslam_ctx* ctx, int n, const float* pts3d, 
     SSLAM_REQUIRE(ctx != nullptr, "sslam_pnp_ransac_host: ctx is NULL");
     SSLAM_REQUIRE(n >= 5, "sslam_pnp_ransac_host: %d correspondences, need >= 5 (4: OpenCV's P3P branch, not covered)", n);
     SSLAM_REQUIRE(pts3d && pts2d && mask_out && Tcw_out, "sslam_pnp_ransac_host: NULL argument");
-    PNArgs a; PNScratch L; char* b;
-    if (int rc = pn_args(ctx, n, K9, Tcw_init16 != nullptr, reproj_px, confidence, max_iters, a, L, b)) return rc;
+    PNArgs a;
+    if (int rc = pn_args(ctx, n, K9, Tcw_init16 != nullptr, reproj_px, confidence, max_iters, a)) return rc;
     hipStream_t s = ctx->stream;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.p3, pts3d, (size_t)n * 12, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.p2, pts2d, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.p3, pts3d, (size_t)n * 3));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.p2, pts2d, (size_t)n * 2));
     pn_enqueue(s, a);
     SSLAM_HIP_CHECK(hipGetLastError());
     int info[4];
-    SSLAM_HIP_CHECK(hipMemcpyAsync(info, b + L.info, 16, hipMemcpyDeviceToHost, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(Tcw_out, b + L.T, 128, hipMemcpyDeviceToHost, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(mask_out, b + L.mask, (size_t)n, hipMemcpyDeviceToHost, s));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, info, a.info_out, 4));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, Tcw_out, a.Tcw_out, 16));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, mask_out, a.mask, (size_t)n));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
     if (info_out) for (int i = 0; i < 4; ++i) info_out[i] = info[i];
     return 0;

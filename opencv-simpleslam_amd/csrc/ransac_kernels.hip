@@ -470,12 +470,7 @@ __global__ __launch_bounds__(1024) void rs_tail_kernel(RSArgs a) {
 // against the 17 of the thread / sample + workgroup / model form (r05 kernel trace: 116 us per call on ~600 matches, 40 of them
 // the eight early-exit launches of the two chunks a matcher's inlier ratios never reach).
 void rs_enqueue(hipStream_t s, RSArgs a, int max_iters, float* p1w, float* p2w) {
-    // the sample loop in chunks: a chunk whose first sample lies beyond the (shrinking) budget is two early-exit launches.
-    // The sample stream is replayed by ONE lane (cv::RNG is sequential: ~1.4 us per 7-point sample), so the first chunk is
-    // small - with the inlier ratios a matcher's output has, OpenCV's budget drops to 3 - 5 after the first all-inlier sample
-    // and the 128-sample first chunk of r03 spent 180 us drawing samples the loop never looks at - and the rest are few and
-    // large: the result does not depend on the chunking.
-    const int bounds[] = {0, std::min(8, max_iters), std::min(128, max_iters), max_iters};
+    const auto bounds = sslam::ransac_chunk_bounds(max_iters, 128);     // (the schedule: geom_slab.hpp)
     const size_t pts_lds = (size_t)std::min(a.n, RS_LDS_POINTS) * 16;
     (void)hipGetLastError();     // (a stale error of another library on this thread is not ours)
     if (a.ij && a.n > RS_LDS_POINTS) {      // too many matches for the head kernel's LDS image: gather in a launch of its own
@@ -494,14 +489,11 @@ void rs_enqueue(hipStream_t s, RSArgs a, int max_iters, float* p1w, float* p2w) 
     hipLaunchKernelGGL(rs_tail_kernel, dim3(1), dim3(1024), 0, s, a);       // (a.h0, a.h1: the last chunk)
 }
 
-struct RSScratch { size_t p1, p2, sub, mod, nm, cnt, med, mask, ctrl, total; };
-RSScratch rs_layout(size_t N, size_t H) {
-    RSScratch L{};
-    sslam::Carver carve;
-    L.p1 = carve(N * 8); L.p2 = carve(N * 8); L.sub = carve(H * RS_MP * 4); L.mod = carve(H * 27 * 8);
-    L.nm = carve(H * 4); L.cnt = carve(H * 12); L.med = carve(H * 12); L.mask = carve(N); L.ctrl = carve(sizeof(RSCtrl));
-    L.total = carve.bytes;
-    return L;
+// the slab-backed pointers of RSArgs, in slab order
+void rs_bind(sslam::Slab& sl, RSArgs& a, size_t N, size_t H) {
+    a.p1 = sl.take<float>(N * 2); a.p2 = sl.take<float>(N * 2); a.subsets = sl.take<int>(H * RS_MP);
+    a.models = sl.take<double>(H * 27); a.nmodels = sl.take<int>(H); a.counts = sl.take<int>(H * 3);
+    a.medians = sl.take<float>(H * 3); a.mask = sl.take<unsigned char>(N); a.ctrl = sl.take<RSCtrl>(1);
 }
 
 }  // namespace
@@ -517,19 +509,13 @@ extern "C" int sslam_fmat_ransac_dev(sslam_ctx* ctx, int n_max, const int32_t* n
     if (confidence < DBL_EPSILON || confidence > 1 - DBL_EPSILON) confidence = 0.99;
     if (max_iters <= 0 || max_iters > RS_MAX_ITERS) max_iters = RS_MAX_ITERS;
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
-    const RSScratch L = rs_layout((size_t)n_max, (size_t)max_iters);
-    char* b;
-    if (int rc = sslam::ctx_scratch(ctx, L.total, &b)) return rc;
-    hipStream_t s = ctx->stream;
     RSArgs a{};
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { rs_bind(sl, a, (size_t)n_max, (size_t)max_iters); })) return rc;
     a.n = n_max; a.n_dev = n_dev; a.max_iters = max_iters; a.thresh = thresh; a.confidence = confidence;
     a.xy1 = xy1_dev; a.xy2 = xy2_dev; a.ij = ij_dev; a.ij_out = ij_out_dev; a.info_out = info_out_dev; a.F_out = F_out_dev;
-    a.p1 = (const float*)(b + L.p1); a.p2 = (const float*)(b + L.p2);
-    a.subsets = (int*)(b + L.sub); a.models = (double*)(b + L.mod); a.nmodels = (int*)(b + L.nm);
-    a.counts = (int*)(b + L.cnt); a.medians = (float*)(b + L.med);
-    a.mask = mask_out_dev ? mask_out_dev : (unsigned char*)(b + L.mask);
-    a.ctrl = (RSCtrl*)(b + L.ctrl);
-    rs_enqueue(s, a, max_iters, (float*)(b + L.p1), (float*)(b + L.p2));
+    float* p1w = const_cast<float*>(a.p1); float* p2w = const_cast<float*>(a.p2);     // (the gather writes them)
+    if (mask_out_dev) a.mask = mask_out_dev;
+    rs_enqueue(ctx->stream, a, max_iters, p1w, p2w);
     SSLAM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -546,24 +532,17 @@ extern "C" int sslam_fmat_ransac_host(sslam_ctx* ctx, int n, const float* pts1, 
     if (max_iters <= 0 || max_iters > RS_MAX_ITERS) max_iters = RS_MAX_ITERS;
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t N = (size_t)n;
-    const RSScratch L = rs_layout(N, (size_t)max_iters);
-    char* b;
-    if (int rc = sslam::ctx_scratch(ctx, L.total, &b)) return rc;
-    const size_t o_p1 = L.p1, o_p2 = L.p2, o_mask = L.mask, o_ctrl = L.ctrl;
-    hipStream_t s = ctx->stream;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + o_p1, pts1, N * 8, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + o_p2, pts2, N * 8, hipMemcpyHostToDevice, s));
     RSArgs a{};
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { rs_bind(sl, a, N, (size_t)max_iters); })) return rc;
+    hipStream_t s = ctx->stream;
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.p1, pts1, N * 2));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.p2, pts2, N * 2));
     a.n = n; a.max_iters = max_iters; a.thresh = thresh; a.confidence = confidence;
-    a.p1 = (const float*)(b + o_p1); a.p2 = (const float*)(b + o_p2);
-    a.subsets = (int*)(b + L.sub); a.models = (double*)(b + L.mod); a.nmodels = (int*)(b + L.nm);
-    a.counts = (int*)(b + L.cnt); a.medians = (float*)(b + L.med); a.mask = (unsigned char*)(b + o_mask);
-    a.ctrl = (RSCtrl*)(b + o_ctrl);
     rs_enqueue(s, a, max_iters, nullptr, nullptr);
     SSLAM_HIP_CHECK(hipGetLastError());
     RSCtrl h{};
-    SSLAM_HIP_CHECK(hipMemcpyAsync(&h, b + o_ctrl, sizeof(RSCtrl), hipMemcpyDeviceToHost, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(mask_out, b + o_mask, N, hipMemcpyDeviceToHost, s));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, &h, a.ctrl, 1));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, mask_out, a.mask, N));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
     if (F_out) for (int i = 0; i < 9; ++i) F_out[i] = h.best_h >= 0 ? h.F[i] : 0.0;
     if (info_out) {

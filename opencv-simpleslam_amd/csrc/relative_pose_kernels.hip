@@ -179,16 +179,12 @@ __global__ __launch_bounds__(RP_TAIL_T) void rp_tail_kernel(RPArgs a) {
     }
 }
 
-struct RPScratch { size_t p1, p2, mask_in, P, masks, counts, rt, mask_out, info, total; };
-RPScratch rp_layout(size_t N, bool with_mask) {
-    RPScratch L{};
-    sslam::Carver carve;
-    L.p1 = carve(N * 8); L.p2 = carve(N * 8);
-    if (with_mask) L.mask_in = carve(N);
-    L.P = carve((48 + 21) * 8); L.masks = carve(4 * N); L.counts = carve(4 * 4);
-    L.rt = carve(12 * 8); L.mask_out = carve(N); L.info = carve(8 * 4);
-    L.total = carve.bytes;
-    return L;
+// the slab-backed pointers of RPArgs, in slab order
+void rp_bind(sslam::Slab& sl, RPArgs& a, size_t N, bool with_mask) {
+    a.p1 = sl.take<float>(N * 2); a.p2 = sl.take<float>(N * 2);
+    if (with_mask) a.mask_in = sl.take<unsigned char>(N);
+    a.P = sl.take<double>(48 + 21); a.masks = sl.take<unsigned char>(4 * N); a.counts = sl.take<int32_t>(4);
+    a.Rt_out = sl.take<double>(12); a.mask_out = sl.take<unsigned char>(N); a.info_out = sl.take<int32_t>(8);
 }
 
 // =================================================================================================================
@@ -311,16 +307,14 @@ __global__ __launch_bounds__(RP_TAIL_T) void tv_tail_kernel(TVArgs a) {
     }
 }
 
-struct TVScratch { size_t p1, p2, sel, idx, cnt, ang, X, z, out, total; };
-TVScratch tv_layout(size_t N, bool with_sel) {
-    TVScratch L{};
-    sslam::Carver carve;
-    L.p1 = carve(N * 8); L.p2 = carve(N * 8);
-    if (with_sel) L.sel = carve(N);
-    L.idx = carve(N * 4); L.cnt = carve(2 * 4); L.ang = carve(N * 8); L.X = carve(N * 24); L.z = carve(N * 16);
-    L.out = carve(2 * 8 + 4 * 4);               // metrics[2], info[4]: one read-back
-    L.total = carve.bytes;
-    return L;
+// the slab-backed pointers of TVArgs, in slab order
+void tv_bind(sslam::Slab& sl, TVArgs& a, size_t N, bool with_sel) {
+    a.p1 = sl.take<float>(N * 2); a.p2 = sl.take<float>(N * 2);
+    if (with_sel) a.sel = sl.take<unsigned char>(N);
+    a.idx = sl.take<int32_t>(N); a.cnt = sl.take<int32_t>(2); a.ang = sl.take<double>(N); a.X = sl.take<double>(N * 3);
+    a.z = sl.take<double>(N * 2);
+    a.metrics_out = sl.take<double>(2 + 2);     // metrics[2], then info[4] in the same piece: one read-back
+    if (a.metrics_out) a.info_out = reinterpret_cast<int32_t*>(a.metrics_out + 2);
 }
 
 }  // namespace
@@ -340,28 +334,23 @@ extern "C" int sslam_recover_pose_host(sslam_ctx* ctx, int n, const float* pts1,
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t N = (size_t)n;
     const bool with_mask = mask_in != nullptr && n > 0;
-    const RPScratch L = rp_layout(N, with_mask);
-    char* b;
-    if (int rc = sslam::ctx_scratch(ctx, L.total, &b)) return rc;
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { rp_bind(sl, a, N, with_mask); })) return rc;
     hipStream_t s = ctx->stream;
     if (n) {
-        SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.p1, pts1, N * 8, hipMemcpyHostToDevice, s));
-        SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.p2, pts2, N * 8, hipMemcpyHostToDevice, s));
-        if (with_mask) SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.mask_in, mask_in, N, hipMemcpyHostToDevice, s));
+        SSLAM_HIP_CHECK(sslam::copy_up(s, a.p1, pts1, N * 2));
+        SSLAM_HIP_CHECK(sslam::copy_up(s, a.p2, pts2, N * 2));
+        if (with_mask) SSLAM_HIP_CHECK(sslam::copy_up(s, a.mask_in, mask_in, N));
     }
-    a.n = n; a.p1 = (const float*)(b + L.p1); a.p2 = (const float*)(b + L.p2);
-    a.mask_in = with_mask ? (const unsigned char*)(b + L.mask_in) : nullptr;
-    a.P = (double*)(b + L.P); a.masks = (unsigned char*)(b + L.masks); a.counts = (int32_t*)(b + L.counts);
-    a.Rt_out = (double*)(b + L.rt); a.mask_out = (unsigned char*)(b + L.mask_out); a.info_out = (int32_t*)(b + L.info);
+    a.n = n;
     (void)hipGetLastError();     // (a stale error of another library on this thread is not ours)
     hipLaunchKernelGGL(rp_head_kernel, dim3(1), dim3(64), 0, s, a);
     if (n) hipLaunchKernelGGL(rp_vote_kernel, dim3(sslam::cdiv(n, RP_T), 4), dim3(RP_T), 0, s, a);
     hipLaunchKernelGGL(rp_tail_kernel, dim3(1), dim3(RP_TAIL_T), 0, s, a);
     SSLAM_HIP_CHECK(hipGetLastError());
     double Rt[12];
-    SSLAM_HIP_CHECK(hipMemcpyAsync(Rt, b + L.rt, sizeof(Rt), hipMemcpyDeviceToHost, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(info_out, b + L.info, 8 * 4, hipMemcpyDeviceToHost, s));
-    if (n) SSLAM_HIP_CHECK(hipMemcpyAsync(mask_out, b + L.mask_out, N, hipMemcpyDeviceToHost, s));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, Rt, a.Rt_out, 12));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, info_out, a.info_out, 8));
+    if (n) SSLAM_HIP_CHECK(sslam::copy_down(s, mask_out, a.mask_out, N));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
     for (int i = 0; i < 9; ++i) R_out9[i] = Rt[i];
     for (int i = 0; i < 3; ++i) t_out3[i] = Rt[9 + i];
@@ -394,29 +383,23 @@ extern "C" int sslam_two_view_metrics_host(sslam_ctx* ctx, int n, const float* p
     for (int i = 0; i < 3; ++i) a.t[i] = t3[i];
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t N = (size_t)n;
-    const TVScratch L = tv_layout(N, sel != nullptr);
-    char* b;
-    if (int rc = sslam::ctx_scratch(ctx, L.total, &b)) return rc;
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { tv_bind(sl, a, N, sel != nullptr); })) return rc;
     hipStream_t s = ctx->stream;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.p1, pts1, N * 8, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.p2, pts2, N * 8, hipMemcpyHostToDevice, s));
-    if (sel) SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.sel, sel, N, hipMemcpyHostToDevice, s));
-    a.n = n; a.p1 = (const float*)(b + L.p1); a.p2 = (const float*)(b + L.p2);
-    a.sel = sel ? (const unsigned char*)(b + L.sel) : nullptr;
-    a.idx = (int32_t*)(b + L.idx); a.cnt = (int32_t*)(b + L.cnt); a.ang = (double*)(b + L.ang);
-    a.X = (double*)(b + L.X); a.z = (double*)(b + L.z);
-    a.metrics_out = (double*)(b + L.out); a.info_out = (int32_t*)(b + L.out + 16);
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.p1, pts1, N * 2));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.p2, pts2, N * 2));
+    if (sel) SSLAM_HIP_CHECK(sslam::copy_up(s, a.sel, sel, N));
+    a.n = n;
     (void)hipGetLastError();
     hipLaunchKernelGGL(tv_select_kernel, dim3(1), dim3(RP_TAIL_T), 0, s, a);
     hipLaunchKernelGGL(tv_point_kernel, dim3(sslam::cdiv(n, RP_T)), dim3(RP_T), 0, s, a);
     hipLaunchKernelGGL(tv_tail_kernel, dim3(1), dim3(RP_TAIL_T), 0, s, a);
     SSLAM_HIP_CHECK(hipGetLastError());
-    char out[32];
-    SSLAM_HIP_CHECK(hipMemcpyAsync(out, b + L.out, sizeof(out), hipMemcpyDeviceToHost, s));
-    if (X_out && selected) SSLAM_HIP_CHECK(hipMemcpyAsync(X_out, b + L.X, selected * 24, hipMemcpyDeviceToHost, s));
-    if (z_out && selected) SSLAM_HIP_CHECK(hipMemcpyAsync(z_out, b + L.z, selected * 16, hipMemcpyDeviceToHost, s));
+    double out[4];
+    SSLAM_HIP_CHECK(sslam::copy_down(s, out, a.metrics_out, 4));
+    if (X_out && selected) SSLAM_HIP_CHECK(sslam::copy_down(s, X_out, a.X, selected * 3));
+    if (z_out && selected) SSLAM_HIP_CHECK(sslam::copy_down(s, z_out, a.z, selected * 2));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
     std::memcpy(metrics_out, out, 16);
-    std::memcpy(info_out, out + 16, 16);
+    std::memcpy(info_out, out + 2, 16);
     return 0;
 }

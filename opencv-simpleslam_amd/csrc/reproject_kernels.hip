@@ -19,7 +19,7 @@ namespace {
 constexpr int RP_MAXC = 128;      // keypoints kept per map point (within radius)
 constexpr int RP_DIM = 128;
 
-struct RPArgs {
+struct RMArgs {
     int Q, N, img_w, img_h;
     double radius2, thr;
     const double* pts;            // [Q][3]
@@ -38,7 +38,7 @@ struct RPArgs {
 };
 
 // one wave per map point: project, collect the keypoints in range (ascending index), score them
-__global__ __launch_bounds__(256) void rp_pairs_kernel(RPArgs a) {
+__global__ __launch_bounds__(256) void rp_pairs_kernel(RMArgs a) {
     __shared__ int list[4][RP_MAXC];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = blockIdx.x * 4 + wave;
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void rp_pairs_kernel(RPArgs a) {
 }
 
 // the greedy pass, in map order (one lane; `used` bitmap in LDS)
-__global__ __launch_bounds__(64) void rp_assign_kernel(RPArgs a) {
+__global__ __launch_bounds__(64) void rp_assign_kernel(RMArgs a) {
     extern __shared__ unsigned used[];
     for (int i = threadIdx.x; i < (a.N + 31) / 32; i += 64) used[i] = 0u;
     __syncthreads();
@@ -129,38 +129,27 @@ __global__ __launch_bounds__(64) void rp_assign_kernel(RPArgs a) {
 
 namespace {
 
-// scratch of one association call, carved from the context's scratch slab
-struct RPScratch { char* base; size_t K, T, uv, cn, ck, cd, out, info, pts, cnt, od, kp, des; };
-
-int rp_scratch(sslam_ctx* ctx, size_t Q, size_t N, bool host_inputs, RPScratch& sc) {
-    sslam::Carver carve;
-    sc.K = carve(72); sc.T = carve(128); sc.uv = carve(Q * 8); sc.cn = carve(Q * 4);
-    sc.ck = carve(Q * RP_MAXC * 4); sc.cd = carve(Q * RP_MAXC * 4); sc.out = carve(Q * 4); sc.info = carve(16);
-    if (host_inputs) {
-        sc.pts = carve(Q * 24); sc.cnt = carve(Q * 4); sc.od = carve(Q * 6 * RP_DIM * 4);
-        sc.kp = carve(N * 8); sc.des = carve(N * RP_DIM * 4);
-    }
-    return sslam::ctx_scratch(ctx, carve.bytes, &sc.base);
+// the slab-backed pointers of RMArgs, in slab order.  host_inputs: the map and keypoint arrays are the slab's too
+void rm_bind(sslam::Slab& sl, RMArgs& a, size_t Q, size_t N, bool host_inputs) {
+    a.K = sl.take<double>(9); a.Tcw = sl.take<double>(16); a.uv = sl.take<float>(Q * 2); a.cand_n = sl.take<int32_t>(Q);
+    a.cand_kp = sl.take<int32_t>(Q * RP_MAXC); a.cand_d = sl.take<float>(Q * RP_MAXC);
+    a.kp_of_point = sl.take<int32_t>(Q); a.info = sl.take<int32_t>(4);
+    if (!host_inputs) return;
+    a.pts = sl.take<double>(Q * 3); a.obs_cnt = sl.take<int32_t>(Q); a.obs_desc = sl.take<float>(Q * 6 * RP_DIM);
+    a.kp = sl.take<float>(N * 2); a.des = sl.take<float>(N * RP_DIM);
 }
 
-// enqueue the two kernels on device-resident inputs; K9 / Tcw16 are host values
-int rp_enqueue(sslam_ctx* ctx, const RPScratch& sc, int n_points, const double* pts_d, const int32_t* cnt_d,
-               const float* desc_d, const double* K9, const double* Tcw16, int n_kp, const float* kp_d, const float* des_d,
-               int img_w, int img_h, double radius_px, double max_dist, int32_t* out_d, float* uv_d, int32_t* info_d) {
+// enqueue the two kernels on device-resident inputs (`a`: every pointer set); K9 / Tcw16 are host values
+int rm_enqueue(sslam_ctx* ctx, RMArgs a, const double* K9, const double* Tcw16, int img_w, int img_h, double radius_px,
+               double max_dist) {
     hipStream_t s = ctx->stream;
-    char* b = sc.base;
     (void)hipGetLastError();     // (a stale error of another library on this thread is not ours)
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + sc.K, K9, 72, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + sc.T, Tcw16, 128, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemsetAsync(info_d, 0, 16, s));
-    RPArgs a{};
-    a.Q = n_points; a.N = n_kp; a.img_w = img_w; a.img_h = img_h; a.radius2 = radius_px * radius_px; a.thr = max_dist;
-    a.pts = pts_d; a.obs_cnt = cnt_d; a.obs_desc = desc_d;
-    a.K = (const double*)(b + sc.K); a.Tcw = (const double*)(b + sc.T); a.kp = kp_d; a.des = des_d;
-    a.uv = uv_d ? uv_d : (float*)(b + sc.uv); a.cand_n = (int32_t*)(b + sc.cn);
-    a.cand_kp = (int32_t*)(b + sc.ck); a.cand_d = (float*)(b + sc.cd); a.kp_of_point = out_d; a.info = info_d;
-    hipLaunchKernelGGL(rp_pairs_kernel, dim3(sslam::cdiv(n_points, 4)), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(rp_assign_kernel, dim3(1), dim3(64), (((size_t)n_kp + 31) / 32) * 4, s, a);
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.K, K9, 9));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.Tcw, Tcw16, 16));
+    SSLAM_HIP_CHECK(hipMemsetAsync(a.info, 0, 16, s));
+    a.img_w = img_w; a.img_h = img_h; a.radius2 = radius_px * radius_px; a.thr = max_dist;
+    hipLaunchKernelGGL(rp_pairs_kernel, dim3(sslam::cdiv(a.Q, 4)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(rp_assign_kernel, dim3(1), dim3(64), (((size_t)a.N + 31) / 32) * 4, s, a);
     SSLAM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -181,10 +170,12 @@ extern "C" int sslam_reproject_match_dev(sslam_ctx* ctx, int n_points, const dou
                   "sslam_reproject_match_dev: NULL argument");
     SSLAM_REQUIRE(radius_px >= 0.0 && img_w > 0 && img_h > 0, "sslam_reproject_match_dev: bad radius / image size");
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
-    RPScratch sc{};
-    if (int rc = rp_scratch(ctx, (size_t)n_points, (size_t)n_kp, false, sc)) return rc;
-    return rp_enqueue(ctx, sc, n_points, pts3d, obs_cnt, obs_desc, K9, Tcw16, n_kp, kp_xy, des, img_w, img_h, radius_px,
-                      max_dist, kp_of_point, uv_out, info_out);
+    RMArgs a{};
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { rm_bind(sl, a, (size_t)n_points, (size_t)n_kp, false); })) return rc;
+    a.Q = n_points; a.N = n_kp; a.pts = pts3d; a.obs_cnt = obs_cnt; a.obs_desc = obs_desc; a.kp = kp_xy; a.des = des;
+    if (uv_out) a.uv = uv_out;
+    a.kp_of_point = kp_of_point; a.info = info_out;
+    return rm_enqueue(ctx, a, K9, Tcw16, img_w, img_h, radius_px, max_dist);
 }
 
 extern "C" int sslam_reproject_match_host(sslam_ctx* ctx, int n_points, const double* pts3d, const int32_t* obs_cnt,
@@ -200,23 +191,18 @@ extern "C" int sslam_reproject_match_host(sslam_ctx* ctx, int n_points, const do
         SSLAM_REQUIRE(obs_cnt[q] >= 0 && obs_cnt[q] <= 6, "sslam_reproject_match_host: obs_cnt[%d]=%d not in [0,6]", q, obs_cnt[q]);
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t Q = (size_t)n_points, N = (size_t)n_kp;
-    RPScratch sc{};
-    if (int rc = rp_scratch(ctx, Q, N, true, sc)) return rc;
-    char* b = sc.base;
+    RMArgs a{};
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { rm_bind(sl, a, Q, N, true); })) return rc;
+    a.Q = n_points; a.N = n_kp;
     hipStream_t s = ctx->stream;
-    auto up = [&](size_t o, const void* src, size_t bytes) { return hipMemcpyAsync(b + o, src, bytes, hipMemcpyHostToDevice, s); };
-    SSLAM_HIP_CHECK(up(sc.pts, pts3d, Q * 24)); SSLAM_HIP_CHECK(up(sc.cnt, obs_cnt, Q * 4));
-    SSLAM_HIP_CHECK(up(sc.od, obs_desc, Q * 6 * RP_DIM * 4));
-    SSLAM_HIP_CHECK(up(sc.kp, kp_xy, N * 8)); SSLAM_HIP_CHECK(up(sc.des, des, N * RP_DIM * 4));
-    if (int rc = rp_enqueue(ctx, sc, n_points, (const double*)(b + sc.pts), (const int32_t*)(b + sc.cnt),
-                            (const float*)(b + sc.od), K9, Tcw16, n_kp, (const float*)(b + sc.kp), (const float*)(b + sc.des),
-                            img_w, img_h, radius_px, max_dist, (int32_t*)(b + sc.out), (float*)(b + sc.uv),
-                            (int32_t*)(b + sc.info)))
-        return rc;
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.pts, pts3d, Q * 3)); SSLAM_HIP_CHECK(sslam::copy_up(s, a.obs_cnt, obs_cnt, Q));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.obs_desc, obs_desc, Q * 6 * RP_DIM));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.kp, kp_xy, N * 2)); SSLAM_HIP_CHECK(sslam::copy_up(s, a.des, des, N * RP_DIM));
+    if (int rc = rm_enqueue(ctx, a, K9, Tcw16, img_w, img_h, radius_px, max_dist)) return rc;
     int32_t info[4] = {0, 0, 0, 0};
-    SSLAM_HIP_CHECK(hipMemcpyAsync(kp_of_point, b + sc.out, Q * 4, hipMemcpyDeviceToHost, s));
-    if (uv_out) SSLAM_HIP_CHECK(hipMemcpyAsync(uv_out, b + sc.uv, Q * 8, hipMemcpyDeviceToHost, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(info, b + sc.info, 16, hipMemcpyDeviceToHost, s));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, kp_of_point, a.kp_of_point, Q));
+    if (uv_out) SSLAM_HIP_CHECK(sslam::copy_down(s, uv_out, a.uv, Q * 2));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, info, a.info, 4));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
     SSLAM_REQUIRE(info[1] == 0, "sslam_reproject_match_host: more than %d keypoints within %.1f px of one projection",
                   RP_MAXC, radius_px);

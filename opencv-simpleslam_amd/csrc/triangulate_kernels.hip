@@ -187,18 +187,13 @@ int tr_fill(TRArgs& a, const char* who, const double* K9, double min_depth, doub
     return 0;
 }
 
-struct TRScratch { size_t reason, xall, p1, p2, T, xout, idx, info, diag, total; };
-TRScratch tr_layout(size_t N, bool host, bool diag) {
-    TRScratch L{};
-    sslam::Carver carve;
-    L.reason = carve(N * 4); L.xall = carve(N * 24);
-    if (host) {
-        L.p1 = carve(N * 8); L.p2 = carve(N * 8); L.T = carve(32 * 8); L.xout = carve(N * 24); L.idx = carve(N * 4);
-        L.info = carve(8 * 4);
-        if (diag) L.diag = carve(N * 40);
-    }
-    L.total = carve.bytes;
-    return L;
+// the slab-backed pointers of TRArgs, in slab order.  host: the inputs and outputs are the slab's too (T1: both poses, [32])
+void tr_bind(sslam::Slab& sl, TRArgs& a, size_t N, bool host, bool diag) {
+    a.reason = sl.take<int32_t>(N); a.Xall = sl.take<double>(N * 3);
+    if (!host) return;
+    a.xy1 = sl.take<float>(N * 2); a.xy2 = sl.take<float>(N * 2); a.T1 = sl.take<double>(32);
+    a.X_out = sl.take<double>(N * 3); a.idx_out = sl.take<int32_t>(N); a.info_out = sl.take<int32_t>(8);
+    if (diag) a.diag = sl.take<double>(N * 5);
 }
 
 }  // namespace
@@ -216,12 +211,9 @@ extern "C" int sslam_triangulate_2view_dev(sslam_ctx* ctx, int n_max, const int3
     TRArgs a{};
     if (int rc = tr_fill(a, who, K9, min_depth, max_depth, use_parallax_gate, parallax_min_deg, reproj_px_max)) return rc;
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
-    const TRScratch L = tr_layout((size_t)n_max, false, false);
-    char* b;
-    if (int rc = sslam::ctx_scratch(ctx, L.total, &b)) return rc;
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { tr_bind(sl, a, (size_t)n_max, false, false); })) return rc;
     a.n = n_max; a.n_dev = n_dev; a.xy1 = xy1_dev; a.xy2 = xy2_dev; a.ij = ij_dev; a.T1 = T1_dev; a.T2 = T2_dev;
-    a.reason = reason_out_dev ? reason_out_dev : (int32_t*)(b + L.reason);
-    a.Xall = (double*)(b + L.xall);
+    if (reason_out_dev) a.reason = reason_out_dev;
     a.diag = diag_out_dev; a.X_out = X_out_dev; a.ij_out = ij_out_dev; a.info_out = info_out_dev;
     tr_enqueue(ctx->stream, a);
     SSLAM_HIP_CHECK(hipGetLastError());
@@ -246,31 +238,25 @@ extern "C" int sslam_triangulate_2view_host(sslam_ctx* ctx, int n, const float* 
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t N = (size_t)n;
     const bool want_diag = diag_out != nullptr;
-    const TRScratch L = tr_layout(N, true, want_diag);
-    char* b;
-    if (int rc = sslam::ctx_scratch(ctx, L.total, &b)) return rc;
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { tr_bind(sl, a, N, true, want_diag); })) return rc;
     hipStream_t s = ctx->stream;
     double Ts[32];
     for (int i = 0; i < 16; ++i) { Ts[i] = T1_16[i]; Ts[16 + i] = T2_16[i]; }
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.p1, pts1, N * 8, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.p2, pts2, N * 8, hipMemcpyHostToDevice, s));
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + L.T, Ts, sizeof(Ts), hipMemcpyHostToDevice, s));
-    a.n = n; a.xy1 = (const float*)(b + L.p1); a.xy2 = (const float*)(b + L.p2);
-    a.T1 = (const double*)(b + L.T); a.T2 = a.T1 + 16;
-    a.reason = (int32_t*)(b + L.reason); a.Xall = (double*)(b + L.xall);
-    a.diag = want_diag ? (double*)(b + L.diag) : nullptr;
-    a.X_out = (double*)(b + L.xout); a.idx_out = (int32_t*)(b + L.idx); a.info_out = (int32_t*)(b + L.info);
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.xy1, pts1, N * 2));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.xy2, pts2, N * 2));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.T1, Ts, 32));
+    a.n = n; a.T2 = a.T1 + 16;
     tr_enqueue(s, a);
     SSLAM_HIP_CHECK(hipGetLastError());
-    SSLAM_HIP_CHECK(hipMemcpyAsync(info_out, b + L.info, 8 * 4, hipMemcpyDeviceToHost, s));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, info_out, a.info_out, 8));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));      // (Ts is a stack array: the copy above must have left it; the count sizes the rest)
     const size_t kept = (size_t)info_out[0];
     if (kept) {
-        SSLAM_HIP_CHECK(hipMemcpyAsync(X_out, b + L.xout, kept * 24, hipMemcpyDeviceToHost, s));
-        SSLAM_HIP_CHECK(hipMemcpyAsync(idx_out, b + L.idx, kept * 4, hipMemcpyDeviceToHost, s));
+        SSLAM_HIP_CHECK(sslam::copy_down(s, X_out, a.X_out, kept * 3));
+        SSLAM_HIP_CHECK(sslam::copy_down(s, idx_out, a.idx_out, kept));
     }
-    if (reason_out) SSLAM_HIP_CHECK(hipMemcpyAsync(reason_out, b + L.reason, N * 4, hipMemcpyDeviceToHost, s));
-    if (want_diag) SSLAM_HIP_CHECK(hipMemcpyAsync(diag_out, b + L.diag, N * 40, hipMemcpyDeviceToHost, s));
+    if (reason_out) SSLAM_HIP_CHECK(sslam::copy_down(s, reason_out, a.reason, N));
+    if (want_diag) SSLAM_HIP_CHECK(sslam::copy_down(s, diag_out, a.diag, N * 5));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
     return 0;
 }
