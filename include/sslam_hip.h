@@ -402,6 +402,34 @@ int sslam_reproject_match_dev(sslam_ctx* ctx, int n_points, const double* pts3d,
                               int img_w, int img_h, double radius_px, double max_dist,
                               int32_t* kp_of_point, float* uv_out, int32_t* info_out);
 
+/* ------------------------------------------------------- brute-force matcher
+ * Replaces `cv2.BFMatcher(norm, crossCheck).match(des0, des1)` as `feature_matcher` calls it on the OpenCV branch
+ * (slam/core/features_utils.py:173-178; the matcher is built at :54-55 with NORM_HAMMING for ORB / AKAZE, NORM_L2 for
+ * SIFT, crossCheck=True): the nearest train row of every query row, with crossCheck only the mutual pairs.
+ *   norm : 6 = NORM_HAMMING: q, t are uint8 [rows][D], D = 1..256 bytes; d = popcount of the XOR, exact
+ *          4 = NORM_L2: q, t are float32 [rows][D], D = 1..512; d = sqrtf(sum_k (a_k - b_k)^2) in float32, the difference
+ *              form, one accumulator per pair, k ascending, acc = fmaf(diff, diff, acc), a correctly rounded root
+ *          (cv2's values; anything else is refused)
+ *   nearest = strictly smallest d, the lowest index on a tie (for L2 compared AFTER the root); a NaN distance, or one not
+ *   below FLT_MAX, never wins, and a row without a winner has no match
+ *   cross_check 0: one match per query row that has a winner;  else: only where the train row's nearest query is that row
+ *   M, N : rows of q and t, 0..65536 each (M == 0 or N == 0: k_out = 0, no device work)
+ *   ij_out[M][2] int32 (queryIdx, trainIdx), ascending queryIdx;  dist_out[M] float32;  k_out : the match count
+ * The M x N distances are never stored: scratch is 8 (M + N) bytes of the context's buffer.  The outputs are bitwise the
+ * same from run to run. */
+int sslam_bf_match_host(sslam_ctx* ctx, int norm, int cross_check, int D, const void* q, int M, const void* t, int N,
+                        int32_t* ij_out, float* dist_out, int32_t* k_out);
+/* Device-pointer variant; enqueue only.  M, N bound the rows of the input arrays; m_dev / n_dev (device int32[1], may be
+ * NULL) carry the actual counts when they are only known on the device (written by sslam_aliked_extract_dev), clamped to
+ * [0, bound]: a negative count is an empty set.  Rows beyond the counts are never read.
+ *   ij_out_dev[M][2], dist_out_dev[M];  info_out_dev[4] int32 = {K, m, n, 0}
+ * ij_out_dev and info_out_dev[0] are what sslam_fmat_ransac_dev takes as ij_dev / n_dev, as sslam_lightglue_match_dev's are.
+ * The context's scratch buffer is (re)allocated when M + N grows: call once with the largest bounds before capturing or
+ * pipelining. */
+int sslam_bf_match_dev(sslam_ctx* ctx, int norm, int cross_check, int D, const void* q_dev, int M, const int32_t* m_dev,
+                       const void* t_dev, int N, const int32_t* n_dev, int32_t* ij_out_dev, float* dist_out_dev,
+                       int32_t* info_out_dev);
+
 /* ------------------------------------------------------------------ ALIKED
  * Replaces `ALIKED(max_num_keypoints=...).eval().to(device)` at
  * slam/core/features_utils.py:25 and `_bgr_to_tensor` + `detector.extract` +

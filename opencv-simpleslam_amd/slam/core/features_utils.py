@@ -17,7 +17,9 @@ downstream); matches likewise `cv2.DMatch` / duck type.
 
 The OpenCV ORB/SIFT/AKAZE + BF/FLANN branch of the reference (cv2 C++, config 1
 "plumbing") is delegated to cv2 when it is installed and raises otherwise: this
-package accelerates the LightGlue path only.  There is no CPU fallback for the
+package accelerates the LightGlue path only.  (`bf_matcher.BFMatcher` is a GPU
+`cv2.BFMatcher` that `feature_matcher` takes as its matcher; the detectors of that
+branch still need cv2.)  There is no CPU fallback for the
 LightGlue path: without the HIP library / an MI355X it raises.
 """
 from __future__ import annotations
