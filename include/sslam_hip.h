@@ -430,6 +430,62 @@ int sslam_bf_match_dev(sslam_ctx* ctx, int norm, int cross_check, int D, const v
                        const void* t_dev, int N, const int32_t* n_dev, int32_t* ij_out_dev, float* dist_out_dev,
                        int32_t* info_out_dev);
 
+/* ----------------------------------------------------------------------- ORB
+ * Replaces `cv2.ORB_create(nfeatures, scaleFactor, nlevels, edgeThreshold, 0, 2, scoreType, 31, fastThreshold)
+ * .detectAndCompute(img, None)` for 8-bit images, the detector of the reference's default configuration
+ * (`--detector orb --matcher bf`, slam/core/features_utils.py:33-55): grey, the INTER_LINEAR_EXACT pyramid (every level
+ * stored with a reflect-101 border of max(edgeThreshold, 22, 4) + 1), FAST-9/16 with OpenCV's corner score, strict
+ * 8-neighbour non-maximum suppression, the border filter, retainBest by FAST score (ties kept), the Harris response (block 7,
+ * k = 0.04, exact integer sums, float32 tail) and retainBest to the level's quota (ties kept), the intensity-centroid angle
+ * through fastAtan2's polynomial, and the 256-bit rotated BRIEF on the 7x7 sigma-2 blurred level.  tests/orb_ref.py restates
+ * every stage and names what could not be confirmed without cv2 (parity is unpinned); the kernels equal it bit for bit.
+ * THE STATED DEVIATION: for patchSize 31 OpenCV samples a learned table of 256 pairs, which is not available here.  The
+ * default pattern is the one OpenCV generates for every other patch size (makeRandomPattern: cv::RNG(0x34985739), 512 points,
+ * x then y of each from uniform(-15, 16)) - the orb_default_pattern entry below returns it: keypoints are meant to equal
+ * cv2's, descriptors are self-consistent (all frame-to-frame matching needs) but NOT interchangeable with descriptors that cv2
+ * computed.  `pattern_or_null`: int8 [512][2] (x, y), every coordinate in -15..15, for a user who has the learned table.
+ * THE ORDER: level ascending, then response descending, then y, then x (OpenCV's own order within a level is unspecified).
+ * Accepted: nfeatures 1..2^20, scale_factor in (1, 2] (rounded to float32 first, as cv2's binding passes it), nlevels 1..16,
+ * edge_threshold >= 3, score_type 0 (HARRIS_SCORE) or 1 (FAST_SCORE), fast_threshold 1..254, 1 <= max_w, max_h <= 16384;
+ * firstLevel 0, WTA_K 2 and patchSize 31 are the only forms and have no argument.  A level with a side below
+ * 2 edge_threshold + 1 yields no keypoints (neither does any later one); that is not an error.
+ * Ties at a cut are never dropped, so a call can return more than nfeatures rows: capacity = the sum over the levels of
+ * ceil(w_l / 2) ceil(h_l / 2) at max_w x max_h (strict NMS leaves no two 8-adjacent survivors) bounds the rows of every
+ * output array of every call.  An instance holds 76 bytes of device memory per row of it (20 of candidate and key arrays,
+ * 56 of the host entry's outputs) beside the two pyramids: 28 MB at 1241 x 376, about 0.5 GB at 4096 x 2160.  The output
+ * position of a keypoint is found by counting the keys of its level below its own, n^2 / 64 comparisons per wavefront for n
+ * survivors in a level: microseconds at quota size (1303 in level 0 at nfeatures 6000), and the worst case - an image whose
+ * ties fill a level's NMS bound, 116 000 at 1241 x 376 - is 1.3e10 comparisons; bounded, not measured. */
+typedef struct sslam_orb sslam_orb;
+int sslam_orb_create(sslam_ctx* ctx, int max_w, int max_h, int nfeatures, double scale_factor, int nlevels,
+                     int edge_threshold, int score_type, int fast_threshold, const int8_t* pattern_or_null, sslam_orb** out);
+int sslam_orb_destroy(sslam_orb* o);
+int sslam_orb_capacity(sslam_orb* o, int* cap);
+int sslam_orb_default_pattern(int8_t* pattern_out);      /* int8 [512][2]; needs no device */
+/* img uint8 [h][w][c], c in {1, 3 (BGR), 4 (BGRA)}, w <= max_w and h <= max_h (a larger image is refused, never clipped).
+ * Out, each with `capacity` rows of which the first *n_out are written (the host entry may also leave unspecified bytes in
+ * later rows): xy float32 [cap][2] level pixel * scale; aux float32 [cap][4] = size (31 * scale), angle (degrees), response,
+ * octave; desc uint8 [cap][32].  One synchronisation, at the end. */
+int sslam_orb_detect_host(sslam_orb* o, const uint8_t* img, int h, int w, int c, float* xy_out, float* aux_out,
+                          uint8_t* desc_out, int32_t* n_out);
+/* Device-pointer variant; enqueue only, no synchronisation.  n_out_dev: device int32[1], the count as
+ * sslam_bf_match_dev reads its m_dev / n_dev; desc_out_dev is its q_dev / t_dev with D = 32 and xy_out_dev is
+ * sslam_fmat_ransac_dev's xy1 / xy2, so ORB -> brute-force match -> F-matrix filter runs without a host round trip.
+ * The matcher's row bounds M, N stop at 65536 while `capacity` is the NMS worst case (361 991 rows at 1241 x 376): hand it
+ * M = N = min(capacity, 65536), and the same as the filter's n_max.  The matcher clamps the device count to its bound, so of a
+ * frame with more keypoints than that (ties on a large frame; a quota never reaches it) only the first 65536 rows in output
+ * order - the finest levels - are matched; the rows beyond stay in the arrays and in the count, unmatched. */
+int sslam_orb_detect_dev(sslam_orb* o, const uint8_t* img_dev, int h, int w, int c, float* xy_out_dev, float* aux_out_dev,
+                         uint8_t* desc_out_dev, int32_t* n_out_dev);
+/* test hooks, after a call.  level_info: info8 = {w, h, stored stride, stored rows, stored (0 / 1), quota, candidate
+ * capacity, border} of a level of the last frame.  stage_read: a stored level back to the host, any pointer may be NULL:
+ * img / blur uint8 [rows][stride] (border included), cand int32 [capacity][4] = x, y, FAST score, response bits (float32;
+ * a quiet NaN where the first cut dropped the candidate) of the *ncand candidates after NMS and the border filter in
+ * arrival order, cuts[2] = the first cut (a FAST score; 0: nothing dropped, 256: everything) and the bits of the second
+ * (a float32 response; -inf: nothing dropped). */
+int sslam_orb_level_info(sslam_orb* o, int level, int* info8);
+int sslam_orb_stage_read(sslam_orb* o, int level, uint8_t* img, uint8_t* blur, int32_t* cand, int32_t* ncand, int32_t* cuts);
+
 /* ------------------------------------------------------------------ ALIKED
  * Replaces `ALIKED(max_num_keypoints=...).eval().to(device)` at
  * slam/core/features_utils.py:25 and `_bgr_to_tensor` + `detector.extract` +

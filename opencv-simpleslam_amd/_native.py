@@ -92,6 +92,14 @@ def _signatures():
                                             vp, vp, vp]),
         "sslam_bf_match_host": (i32, [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp]),
         "sslam_bf_match_dev": (i32, [vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]),
+        "sslam_orb_create": (i32, [vp, i32, i32, i32, C.c_double, i32, i32, i32, i32, vp, c_void_pp]),
+        "sslam_orb_destroy": (i32, [vp]),
+        "sslam_orb_capacity": (i32, [vp, c_int_p]),
+        "sslam_orb_default_pattern": (i32, [vp]),
+        "sslam_orb_detect_host": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "sslam_orb_detect_dev": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "sslam_orb_level_info": (i32, [vp, i32, vp]),
+        "sslam_orb_stage_read": (i32, [vp, i32, vp, vp, vp, vp, vp]),
         "sslam_aliked_create": (i32, [vp, vp, sz, i32, i32, i32, c_void_pp]),
         "sslam_aliked_create_batched": (i32, [vp, vp, sz, i32, i32, i32, i32, c_void_pp]),
         "sslam_aliked_extract_batch_dev": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]),

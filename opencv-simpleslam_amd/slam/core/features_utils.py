@@ -16,10 +16,10 @@ OpenCV is importable, otherwise the duck type in .types (only `.pt` is read
 downstream); matches likewise `cv2.DMatch` / duck type.
 
 The OpenCV ORB/SIFT/AKAZE + BF/FLANN branch of the reference (cv2 C++, config 1
-"plumbing") is delegated to cv2 when it is installed and raises otherwise: this
-package accelerates the LightGlue path only.  (`bf_matcher.BFMatcher` is a GPU
-`cv2.BFMatcher` that `feature_matcher` takes as its matcher; the detectors of that
-branch still need cv2.)  There is no CPU fallback for the
+"plumbing") is delegated to cv2 when it is installed.  Without cv2 its default,
+`--detector orb --matcher bf`, runs on the GPU (`orb.ORB_create` +
+`bf_matcher.BFMatcher`; orb.py states how its descriptors deviate from cv2's);
+SIFT, AKAZE and FLANN raise.  There is no CPU fallback for the
 LightGlue path: without the HIP library / an MI355X it raises.
 """
 from __future__ import annotations
@@ -93,6 +93,12 @@ def init_feature_pipeline(args):
         matcher._feature_ring.attach_matcher(matcher)
         return detector, matcher
     if not HAVE_CV2:
+        # the branch's default, ORB + brute force, runs on the GPU without OpenCV (orb.py, bf_matcher.py); SIFT, AKAZE and FLANN
+        # stay OpenCV-only
+        if getattr(args, "detector", "orb") == "orb" and getattr(args, "matcher", "bf") != "flann":
+            from ... import bf_matcher, orb
+            return (orb.ORB_create(int(getattr(args, "max_features", 6000)), max_h=MAX_IMAGE_H, max_w=MAX_IMAGE_W),
+                    bf_matcher.BFMatcher(bf_matcher.NORM_HAMMING, crossCheck=True))
         raise ImportError("the OpenCV detector/matcher branch needs cv2; this backend accelerates "
                           "the --use_lightglue path only")
     import cv2
