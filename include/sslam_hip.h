@@ -486,6 +486,62 @@ int sslam_orb_detect_dev(sslam_orb* o, const uint8_t* img_dev, int h, int w, int
 int sslam_orb_level_info(sslam_orb* o, int level, int* info8);
 int sslam_orb_stage_read(sslam_orb* o, int level, uint8_t* img, uint8_t* blur, int32_t* cand, int32_t* ncand, int32_t* cuts);
 
+/* ---------------------------------------------------------------------- SIFT
+ * Replaces `cv2.SIFT_create(nfeatures, nOctaveLayers, contrastThreshold, edgeThreshold, sigma).detectAndCompute(img, None)`
+ * for 8-bit images, the float-descriptor detector of the reference's OpenCV branch (`--detector sift`,
+ * slam/core/features_utils.py:33-55): grey, the doubled base image (firstOctave -1), the Gaussian scale space of
+ * nOctaveLayers + 3 layers per octave (each layer blurred from the one before it, reflect-101), the DoG, the 26-neighbour
+ * extrema with ties, adjustLocalExtrema with the contrast and edge tests, the 36-bin orientation histogram with its peaks,
+ * removeDuplicatedSorted, retainBest(nfeatures) with ties kept (0: no cut), and the 4 x 4 x 8 descriptor as float32 rows of
+ * 128 integer values.  tests/sift_ref.py restates every stage and names what could not be confirmed without cv2 (parity is
+ * unpinned); the kernels equal it bit for bit.
+ * THE DEFINED ARITHMETIC: float32, one IEEE operation at a time; exp, pow, cos, sin are the float64 function of the float32
+ * argument rounded once; the two histograms are sums of 64-bit integers at the scale 2^32 (exact and order-free), converted
+ * back to float32 once - a stated departure from OpenCV's build-dependent float accumulation.
+ * THE ORDER: KeyPoint_LessThan's - x, y ascending, size descending, angle ascending (OpenCV's own order after retainBest is
+ * unspecified).  Duplicates (same pt, size, angle) are dropped before the quota; ties at the quota are kept, so a call can
+ * return more than nfeatures rows.
+ * Accepted: nfeatures 0..2^20, n_octave_layers 1..8, contrast_threshold > 0, edge_threshold > 0, sigma in (0.5, 8],
+ * 1 <= max_w, max_h <= 16384; descriptorType CV_32F and enable_precise_upscale false are the only forms and have no argument.
+ * An octave with a side <= 10 yields nothing and an image too small for an octave yields no keypoint; neither is an error.
+ * CAPACITIES: extrema have no NMS-style bound (ties are candidates).  An instance holds max_candidates extrema (0: one per
+ * 32 pixels of the doubled max_w x max_h frame, at least 1024) and max_keypoints rows (0: the same, or max(4 nfeatures,
+ * 16384) if that is less) - the keypoints after the orientation, before duplicates and the quota, which bound the rows of
+ * every output array.  A frame that exceeds either is VOIDED, never truncated: the device count is 0, a sticky per-instance
+ * word is set (sslam_sift_overflow: bit 0 candidates, bit 1 rows; it is never cleared) and the host entry returns 3 with a
+ * message that names the counts the frame needed.
+ * DEVICE MEMORY, by arithmetic: 2 L + 5 float planes of the doubled frame x 4/3 (Gaussian and DoG slabs) + 2 planes of
+ * temporaries, 208 bytes per candidate and 576 per row: about 0.15 GB at 1241 x 376 and 2.6 GB at 4096 x 2160 at nfeatures
+ * 6000 (3.2 GB at nfeatures 0, where the rows default to the candidates).  SSLAM_MAX_IMAGE_H / _W shrink it, as for ORB. */
+typedef struct sslam_sift sslam_sift;
+int sslam_sift_create(sslam_ctx* ctx, int max_w, int max_h, int nfeatures, int n_octave_layers, double contrast_threshold,
+                      double edge_threshold, double sigma, int max_candidates, int max_keypoints, sslam_sift** out);
+int sslam_sift_destroy(sslam_sift* o);
+int sslam_sift_capacity(sslam_sift* o, int* rows, int* candidates_or_null);
+int sslam_sift_overflow(sslam_sift* o, int* word);       /* the sticky word; synchronises the stream */
+/* img uint8 [h][w][c], c in {1, 3 (BGR), 4 (BGRA)}, w <= max_w and h <= max_h (a larger image is refused, never clipped).
+ * Out, each with `rows` rows of which the first *n_out are written: xy float32 [rows][2]; aux float32 [rows][3] = size,
+ * angle (degrees), response; octave int32 [rows], cv2's packed field (octave byte -1 = 255 for the doubled octave, layer
+ * << 8, cvRound((xi + 0.5) 255) << 16); desc float32 [rows][128].  Two synchronisations (the count, then the rows). */
+int sslam_sift_detect_host(sslam_sift* o, const uint8_t* img, int h, int w, int c, float* xy_out, float* aux_out,
+                           int32_t* octave_out, float* desc_out, int32_t* n_out);
+/* Device-pointer variant; enqueue only, no synchronisation.  n_out_dev: device int32[1], the count as sslam_bf_match_dev
+ * reads its m_dev / n_dev; desc_out_dev is its q_dev / t_dev with NORM_L2 and D = 128 and xy_out_dev is
+ * sslam_fmat_ransac_dev's xy1 / xy2, so SIFT -> brute-force match -> F-matrix filter runs without a host round trip.  The
+ * matcher's row bounds stop at 65536: hand it M = N = min(rows, 65536), as for ORB.  A voided frame writes the count 0. */
+int sslam_sift_detect_dev(sslam_sift* o, const uint8_t* img_dev, int h, int w, int c, float* xy_out_dev, float* aux_out_dev,
+                          int32_t* octave_out_dev, float* desc_out_dev, int32_t* n_out_dev);
+/* test hooks, after a call.  octave_info: info8 = {w, h, octaves computed, Gaussian layers, has an interior (0 / 1), the
+ * integer contrast threshold, max_candidates, max_keypoints} of an octave of the last frame (w = h = 0 beyond the last).
+ * stage_read: any pointer may be NULL: gauss float32 [L + 3][h][w] and dog float32 [L + 2][h][w] of the octave; of the whole
+ * frame, in arrival order: cand int32 [max_candidates][4] = octave, layer, r, c; ref int32 [max_candidates][8] = passed
+ * (0 / 1), r, c, layer after the refinement, the packed octave field, and the float32 bits of x, y, size in the frame of the
+ * doubled image; hist float32 [max_candidates][40] = the smoothed orientation histogram and, at [36], the response (rows of
+ * candidates that did not pass are unspecified); counts[4] = extrema, keypoints before duplicates, output rows, 0. */
+int sslam_sift_octave_info(sslam_sift* o, int octave, int* info8);
+int sslam_sift_stage_read(sslam_sift* o, int octave, float* gauss, float* dog, int32_t* cand, int32_t* ref, float* hist,
+                          int32_t* counts);
+
 /* ------------------------------------------------------------------ ALIKED
  * Replaces `ALIKED(max_num_keypoints=...).eval().to(device)` at
  * slam/core/features_utils.py:25 and `_bgr_to_tensor` + `detector.extract` +
