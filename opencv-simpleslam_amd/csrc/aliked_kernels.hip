@@ -1969,7 +1969,7 @@ struct sslam_aliked {
     int max_frames = 1;               // frames per batched launch sequence (workspace blocks)
     size_t fs = 0;                    // bytes between the workspace blocks of consecutive frames
     int Hp_cap = 0, Wp_cap = 0;
-    sslam::Arena arena;
+    sslam::OwnedSlab slab;
     float* blob = nullptr;
     // weights
     ALConvW b1c1, b1c2, b2c1, b2c2;
@@ -2148,7 +2148,7 @@ int sslam_aliked_create_batched(sslam_ctx* ctx, const float* weights, size_t n_f
     SSLAM_REQUIRE(max_kpts >= 1 && max_kpts <= SEL_CAP, "sslam_aliked_create: max_kpts %d not in [1, %d]", max_kpts,
                   SEL_CAP);
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
-    sslam_aliked* g = new sslam_aliked();
+    std::unique_ptr<sslam_aliked> g(new sslam_aliked());
     g->ctx = ctx; g->max_h = max_h; g->max_w = max_w; g->max_kpts = max_kpts; g->max_frames = max_frames;
     g->kp = sslam::al_kpt_plan(max_kpts);
     // the network never runs larger than AL_LONG_SIDE on the long side (+ padding to a multiple of AL_PAD_DIV)
@@ -2156,7 +2156,7 @@ int sslam_aliked_create_batched(sslam_ctx* ctx, const float* weights, size_t n_f
     const sslam::ALExtents e = sslam::al_extents((size_t)g->Hp_cap * g->Wp_cap, (size_t)max_h * max_w, (size_t)max_kpts);
     g->cand_cap = sslam::CAND_CAP;
     // shared by all frames: weights, their re-ordered copies, the blur taps
-    auto carve_shared = [&](sslam::Arena& A) {
+    auto bind_shared = [&](sslam::Slab& A) {
         g->blob = A.take<float>(n_floats);
         g->d_sf_s = A.take<_Float16>(2 * 128 * 128); g->d_agg_s = A.take<_Float16>((size_t)2 * 128 * 2048);
         g->b2c2f = A.take<_Float16>(2 * 32 * 288);
@@ -2169,7 +2169,7 @@ int sslam_aliked_create_batched(sslam_ctx* ctx, const float* weights, size_t n_f
         g->range_sticky = A.take<int>(4);
     };
     // one workspace block per frame of a batch (frame f's copy of a buffer = frame 0's + f * g->fs bytes)
-    auto carve_frame = [&](sslam::Arena& A) {
+    auto bind_frame = [&](sslam::Slab& A) {
         g->ctrl = A.take<ALCtrl>(e.ctrl);
         g->in_u8 = A.take<uint8_t>(e.in_u8);
         g->fsrc = A.take<float>(e.fsrc); g->img = A.take<float>(e.img);
@@ -2193,23 +2193,21 @@ int sslam_aliked_create_batched(sslam_ctx* ctx, const float* weights, size_t n_f
         g->out_xy = A.take<float>(e.out_xy); g->out_desc = A.take<float>(e.out_desc); g->out_score = A.take<float>(e.out_score);
         g->out_n = A.take<int32_t>(e.out_n);
     };
-    sslam::Arena probe;
-    probe.measure();
-    carve_shared(probe);
-    const size_t shared_bytes = (probe.off + 4095) / 4096 * 4096;
-    probe.off = 0;
-    carve_frame(probe);
-    g->fs = (probe.off + 4095) / 4096 * 4096;
-    if (g->arena.init(shared_bytes + g->fs * (size_t)max_frames + 4096)) { delete g; return 1; }
-    carve_shared(g->arena);
-    g->arena.off = shared_bytes;               // frame 0's block starts on a page boundary; blocks 1.. follow at g->fs
-    carve_frame(g->arena);
-    if (g->out_n == nullptr) {                 // (release before reporting: the batched workspace is GBs)
-        g->arena.release(); delete g;
-        SSLAM_REQUIRE(false, "sslam_aliked_create: workspace arena exhausted");
-    }
+    sslam::Slab ms, mf;
+    bind_shared(ms);
+    bind_frame(mf);
+    const size_t shared_bytes = sslam::align_up(ms.bytes, 4096);
+    g->fs = sslam::align_up(mf.bytes, 4096);
+    // one piece holds both: the shared pieces at its start, frame 0's block on the page boundary behind them, blocks 1.. at g->fs
+    if (int rc = g->slab.alloc("sslam_aliked_create", true, [&](sslam::Slab& S) {
+            char* all = S.take<char>(shared_bytes + g->fs * (size_t)max_frames);
+            if (!all) return;
+            sslam::Slab sh{all}, f0{all + shared_bytes};
+            bind_shared(sh);
+            bind_frame(f0);
+        })) return rc;
     SSLAM_HIP_CHECK(hipMemcpy(g->blob, weights, n_floats * 4, hipMemcpyHostToDevice));
-    if (int rc = al_bind_weights(g, n_floats)) { g->arena.release(); delete g; return rc; }
+    if (int rc = al_bind_weights(g.get(), n_floats)) return rc;
     {   // split-precision weight fragments of the matrix-core kernels (once)
         hipStream_t s = ctx->stream;
         SSLAM_HIP_CHECK(hipMemsetAsync(g->range_sticky, 0, 4 * sizeof(int), s));
@@ -2229,16 +2227,13 @@ int sslam_aliked_create_batched(sslam_ctx* ctx, const float* weights, size_t n_f
         int wflag = 0;
         SSLAM_HIP_CHECK(hipMemcpyAsync(&wflag, g->range_sticky, sizeof(int), hipMemcpyDeviceToHost, s));
         SSLAM_HIP_CHECK(hipStreamSynchronize(s));
-        if (wflag) {
-            g->arena.release(); delete g;
-            SSLAM_REQUIRE(false, "sslam_aliked_create: a weight (BN scale folded) with |value| >= 65520 does not fit the fp16 planes "
-                                 "of the split-precision stages");
-        }
+        SSLAM_REQUIRE(!wflag, "sslam_aliked_create: a weight (BN scale folded) with |value| >= 65520 does not fit the fp16 planes "
+                              "of the split-precision stages");
     }
     SSLAM_HIP_CHECK(hipFuncSetAttribute((const void*)al_block2_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)B2_LDS));
     SSLAM_HIP_CHECK(hipFuncSetAttribute((const void*)al_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SEL_LDS));
     sslam::ctx_retain(ctx);
-    *out = g;
+    *out = g.release();
     return 0;
 }
 
@@ -2248,14 +2243,7 @@ int sslam_aliked_create(sslam_ctx* ctx, const float* weights, size_t n_floats, i
 }
 
 int sslam_aliked_destroy(sslam_aliked* g) {
-    if (!g) return 0;
-    (void)hipStreamSynchronize(g->ctx->stream);
-    g->graphs.clear();
-    g->arena.release();
-    sslam_ctx* ctx = g->ctx;
-    delete g;
-    sslam::ctx_release(ctx);
-    return 0;
+    return sslam::destroy_instance(g);
 }
 
 static int al_check_image(sslam_aliked* g, int H, int W, int C, int max_kpts) {

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -36,32 +37,28 @@ void set_error(const char* fmt, ...);
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// Slab's placement rule as byte offsets, for the KLT and undistort instances, which lay out slabs of their own.
-struct Carver : Slab {
-    size_t operator()(size_t n) { const size_t o = bytes; take<char>(n); return o; }
-};
-
-// Bump allocator over one hipMalloc'd slab: every instance sizes its workspace
-// once at create time, so the launch path never calls hipMalloc (graph-safe).
-struct Arena {
+// An instance's own slab: every instance sizes its memory once at create time, so the launch path never calls hipMalloc
+// (graph-safe).  alloc() is the instance's slab step: `bind(Slab&)` measures, one hipMalloc of that many bytes (zeroed when
+// `zero`), `bind` runs again on it.  The memory goes with the owner.
+struct OwnedSlab {
     char* base = nullptr;
-    size_t cap = 0, off = 0;
-    bool dry = false;   // measuring pass: take() only advances `off`
-    void measure() { dry = true; cap = ~(size_t)0; off = 0; base = nullptr; }
-    int init(size_t bytes) {
-        dry = false;
-        cap = bytes;
-        off = 0;
-        SSLAM_HIP_CHECK(hipMalloc((void**)&base, bytes));
-        SSLAM_HIP_CHECK(hipMemset(base, 0, bytes));
+    OwnedSlab() = default;
+    OwnedSlab(const OwnedSlab&) = delete;
+    OwnedSlab& operator=(const OwnedSlab&) = delete;
+    ~OwnedSlab() { release(); }
+    template <typename Bind>
+    int alloc(const char* who, bool zero, Bind&& bind) {
+        Slab m, s;
+        bind(m);
+        if (const hipError_t e = hipMalloc((void**)&base, m.bytes); e != hipSuccess) {
+            base = nullptr;
+            set_error("%s: %zu bytes of instance memory: %s", who, m.bytes, hipGetErrorString(e));
+            return 1;
+        }
+        if (zero) SSLAM_HIP_CHECK(hipMemset(base, 0, m.bytes));
+        s.base = base;
+        bind(s);
         return 0;
-    }
-    template <typename T>
-    T* take(size_t n) {
-        size_t o = align_up(off, 256);
-        if (o + n * sizeof(T) > cap) return nullptr;
-        off = o + n * sizeof(T);
-        return reinterpret_cast<T*>(base + o);
     }
     void release() {
         if (base) (void)hipFree(base);
@@ -121,6 +118,10 @@ struct GraphCache {
     uint64_t clock = 0;
     size_t cap = 128;
     uint64_t hits = 0, misses = 0;
+    GraphCache() = default;
+    GraphCache(const GraphCache&) = delete;
+    GraphCache& operator=(const GraphCache&) = delete;
+    ~GraphCache() { clear(); }               // (the owner has drained the stream: destroy_instance)
     const std::vector<hipGraphExec_t>* find(const std::vector<uint64_t>& key) {
         for (auto& e : entries)
             if (e.key == key) { e.stamp = ++clock; ++hits; return &e.execs; }
@@ -202,6 +203,17 @@ struct sslam_ctx {
 namespace sslam {
 void ctx_retain(sslam_ctx* ctx);
 void ctx_release(sslam_ctx* ctx);      // frees a closed context when its last instance goes
+// sslam_xxx_destroy of every instance: drain the context's stream (queued work may still use the instance), delete it (its
+// destructor frees what it owns), let go of the context.  NULL: no-op.
+template <typename Instance>
+int destroy_instance(Instance* g) {
+    if (!g) return 0;
+    sslam_ctx* ctx = g->ctx;
+    (void)hipStreamSynchronize(ctx->stream);
+    delete g;
+    ctx_release(ctx);
+    return 0;
+}
 // *base = the context's scratch slab, grown to `bytes` first when it is smaller.  Growing drains the context's stream
 // (work enqueued earlier may still use the old slab) and reallocates: a pipeline sizes it once, with its largest problem.
 int ctx_scratch(sslam_ctx* ctx, size_t bytes, char** base);

@@ -60,7 +60,7 @@ struct sslam_klt {
     int max_w = 0, max_h = 0, max_points = 0, ww = 0, wh = 0, max_level = 0;
     KltFrame fr[2];
     int cur = 0;                 // fr[cur] is the current frame, fr[cur ^ 1] the previous one
-    char* slab = nullptr;
+    sslam::OwnedSlab slab;
     // workspace of the host entries and of the fused stage, each [max_points]
     float *prev = nullptr, *init = nullptr, *next = nullptr, *back = nullptr, *err = nullptr, *err_back = nullptr;
     float *pts0 = nullptr, *pts1 = nullptr;
@@ -375,9 +375,22 @@ size_t klt_padded(const sslam_klt* k, int w, int h) { return (size_t)(w + 2 * k-
 
 uint8_t* klt_interior(const sslam_klt* k, const KltLevel& L) { return L.img + (size_t)k->wh * (L.w + 2 * k->ww) + k->ww; }
 
-void klt_free(sslam_klt* k) {
-    if (k->slab) (void)hipFree(k->slab);
-    delete k;
+// the slab-backed pointers of the instance, in slab order
+void klt_bind(sslam_klt* k, sslam::Slab& S) {
+    for (int f = 0; f < 2; ++f) {
+        int w = k->max_w, h = k->max_h;
+        for (int l = 0; l <= k->max_level; ++l) {        // (every level up to maxLevel at the largest size: the stop rule is per frame)
+            k->fr[f].lv[l].img = S.take<uint8_t>(klt_padded(k, w, h));
+            k->fr[f].lv[l].der = S.take<uint32_t>(klt_padded(k, w, h));
+            w = (w + 1) / 2; h = (h + 1) / 2;
+        }
+    }
+    const size_t np = (size_t)k->max_points;
+    k->prev = S.take<float>(2 * np); k->init = S.take<float>(2 * np); k->next = S.take<float>(2 * np);
+    k->back = S.take<float>(2 * np); k->pts0 = S.take<float>(2 * np); k->pts1 = S.take<float>(2 * np);
+    k->err = S.take<float>(np); k->err_back = S.take<float>(np);
+    k->status = S.take<uint8_t>(np); k->st_back = S.take<uint8_t>(np); k->mask = S.take<uint8_t>(np);
+    k->counts = S.take<int>(5);
 }
 
 int klt_check_image(const char* who, sslam_klt* k, const uint8_t* img, int h, int w, int c) {
@@ -487,50 +500,16 @@ extern "C" int sslam_klt_create(sslam_ctx* ctx, int max_w, int max_h, int max_po
                   "%s: window %dx%d outside %d..%d", who, win_w, win_h, KLT_MIN_WIN, KLT_MAX_WIN);
     SSLAM_REQUIRE(max_level >= 0 && max_level < KLT_MAX_LEVELS, "%s: maxLevel %d outside 0..%d", who, max_level, KLT_MAX_LEVELS - 1);
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
-    sslam_klt* k = new sslam_klt;
+    std::unique_ptr<sslam_klt> k(new sslam_klt);
     k->ctx = ctx; k->max_w = max_w; k->max_h = max_h; k->max_points = max_points; k->ww = win_w; k->wh = win_h; k->max_level = max_level;
-    sslam::Carver carve;
-    size_t o_img[2][KLT_MAX_LEVELS], o_der[2][KLT_MAX_LEVELS];
-    for (int f = 0; f < 2; ++f) {
-        int w = max_w, h = max_h;
-        for (int l = 0; l <= max_level; ++l) {           // (every level up to maxLevel at the largest size: the stop rule is per frame)
-            o_img[f][l] = carve(klt_padded(k, w, h));
-            o_der[f][l] = carve(klt_padded(k, w, h) * 4);
-            w = (w + 1) / 2; h = (h + 1) / 2;
-        }
-    }
-    const size_t np = (size_t)max_points;
-    const size_t o_prev = carve(np * 8), o_init = carve(np * 8), o_next = carve(np * 8), o_back = carve(np * 8), o_p0 = carve(np * 8),
-                 o_p1 = carve(np * 8), o_err = carve(np * 4), o_errb = carve(np * 4), o_st = carve(np), o_stb = carve(np),
-                 o_mask = carve(np), o_cnt = carve(5 * sizeof(int));
-    if (const hipError_t e = hipMalloc((void**)&k->slab, carve.bytes); e != hipSuccess) {
-        sslam::set_error("%s: %zu bytes for %dx%d, %d levels, %d points: %s", who, carve.bytes, max_w, max_h, max_level + 1, max_points,
-                         hipGetErrorString(e));
-        klt_free(k);
-        return 1;
-    }
-    for (int f = 0; f < 2; ++f)
-        for (int l = 0; l <= max_level; ++l) {
-            k->fr[f].lv[l].img = (uint8_t*)(k->slab + o_img[f][l]);
-            k->fr[f].lv[l].der = (uint32_t*)(k->slab + o_der[f][l]);
-        }
-    k->prev = (float*)(k->slab + o_prev); k->init = (float*)(k->slab + o_init); k->next = (float*)(k->slab + o_next);
-    k->back = (float*)(k->slab + o_back); k->pts0 = (float*)(k->slab + o_p0); k->pts1 = (float*)(k->slab + o_p1);
-    k->err = (float*)(k->slab + o_err); k->err_back = (float*)(k->slab + o_errb);
-    k->status = (uint8_t*)(k->slab + o_st); k->st_back = (uint8_t*)(k->slab + o_stb); k->mask = (uint8_t*)(k->slab + o_mask);
-    k->counts = (int*)(k->slab + o_cnt);
+    if (int rc = k->slab.alloc(who, false, [&](sslam::Slab& S) { klt_bind(k.get(), S); })) return rc;
     sslam::ctx_retain(ctx);
-    *out = k;
+    *out = k.release();
     return 0;
 }
 
 extern "C" int sslam_klt_destroy(sslam_klt* k) {
-    if (!k) return 0;
-    (void)hipStreamSynchronize(k->ctx->stream);
-    sslam_ctx* ctx = k->ctx;
-    klt_free(k);
-    sslam::ctx_release(ctx);
-    return 0;
+    return sslam::destroy_instance(k);
 }
 
 extern "C" int sslam_klt_push_dev(sslam_klt* k, const uint8_t* img, int h, int w, int c) {
@@ -559,16 +538,14 @@ extern "C" int sslam_klt_gray_host(sslam_ctx* ctx, const uint8_t* img, int h, in
     SSLAM_REQUIRE(w >= 1 && w <= KLT_MAX_SIDE && h >= 1 && h <= KLT_MAX_SIDE, "%s: frame size %dx%d outside 1..%d", who, w, h, KLT_MAX_SIDE);
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t n = (size_t)h * w;
-    sslam::Carver carve;
-    const size_t o_src = carve(n * c), o_dst = carve(n);
-    char* b;
-    if (int rc = sslam::ctx_scratch(ctx, carve.bytes, &b)) return rc;
+    uint8_t *src = nullptr, *dst = nullptr;
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& S) { src = S.take<uint8_t>(n * c); dst = S.take<uint8_t>(n); })) return rc;
     hipStream_t s = ctx->stream;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + o_src, img, n * c, hipMemcpyHostToDevice, s));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, src, img, n * c));
     (void)hipGetLastError();
-    hipLaunchKernelGGL(klt_gray_kernel, dim3(klt_blocks(n)), dim3(KLT_T), 0, s, (const uint8_t*)(b + o_src), h, w, c, (uint8_t*)(b + o_dst), w);
+    hipLaunchKernelGGL(klt_gray_kernel, dim3(klt_blocks(n)), dim3(KLT_T), 0, s, (const uint8_t*)src, h, w, c, dst, w);
     SSLAM_HIP_CHECK(hipGetLastError());
-    SSLAM_HIP_CHECK(hipMemcpyAsync(gray, b + o_dst, n, hipMemcpyDeviceToHost, s));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, gray, dst, n));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
     return 0;
 }

@@ -1967,7 +1967,7 @@ struct sslam_lightglue {
     int KSmax = 4;                   // key split the attention partial buffers are sized for
     float depth_conf = 0.95f, width_conf = 0.99f, filter_thr = 0.1f;
     int prune_min = -1;
-    sslam::Arena arena;
+    sslam::OwnedSlab slab;
     float* blob = nullptr;
     const float *w_in, *b_in, *w_r;
     LGLayerW L[NL];
@@ -2005,6 +2005,10 @@ struct sslam_lightglue {
     bool use_graphs = false;        // replay the launch sequence of a (batched) device call as a cached hipGraph
     sslam::GraphCache graphs;
     void settings_changed() { if (!graphs.entries.empty()) { (void)hipStreamSynchronize(ctx->stream); graphs.clear(); } }
+    ~sslam_lightglue() {            // what the instance owns besides its slab and its graphs
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        if (zero_plane) (void)hipFree(zero_plane);
+    }
 };
 
 namespace {
@@ -2512,7 +2516,7 @@ int sslam_lightglue_create_batched(sslam_ctx* ctx, const float* weights, size_t 
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
     lg_configure_kernels();
     if (int rc = lg_load_attention_asm(ctx->device)) return rc;
-    sslam_lightglue* g = new sslam_lightglue();
+    std::unique_ptr<sslam_lightglue> g(new sslam_lightglue());
     g->ctx = ctx;
     const int Kc = (max_kpts + 127) / 128 * 128;     // whole attention / GEMM row blocks
     g->Kc = Kc;
@@ -2520,7 +2524,7 @@ int sslam_lightglue_create_batched(sslam_ctx* ctx, const float* weights, size_t 
     g->KSmax = sslam::lg_ks_max(Kc);
     if (const char* e = getenv("SSLAM_LG_SIM_EXACT")) g->hooks.sim_exact = e[0] == '1';
     const size_t K = (size_t)Kc, NI = (size_t)g->NIc, NB = (size_t)max_pairs;
-    auto carve = [&](sslam::Arena& A) {
+    auto bind = [&](sslam::Slab& A) {
         g->blob = A.take<float>(n_floats);
         g->ctrl = A.take<LGCtrl>(NB); g->ctrl_shadow = A.take<LGCtrl>(NB);
         g->range_sticky = A.take<int>(4);
@@ -2557,14 +2561,9 @@ int sslam_lightglue_create_batched(sslam_ctx* ctx, const float* weights, size_t 
         g->ks_hi = A.take<_Float16>(NI * K * D); g->ks_lo = A.take<_Float16>(NI * K * D);
         g->vts_hi = A.take<_Float16>(NI * K * D); g->vts_lo = A.take<_Float16>(NI * K * D);
     };
-    sslam::Arena probe;
-    probe.measure();
-    carve(probe);
-    if (g->arena.init(probe.off + 256)) { delete g; return 1; }
-    carve(g->arena);
-    SSLAM_REQUIRE(g->vts_lo != nullptr, "sslam_lightglue_create: workspace arena exhausted");
+    if (int rc = g->slab.alloc("sslam_lightglue_create", true, bind)) return rc;
     SSLAM_HIP_CHECK(hipMemcpy(g->blob, weights, n_floats * 4, hipMemcpyHostToDevice));
-    if (int rc = lg_bind_weights(g, n_floats)) { g->arena.release(); delete g; return rc; }
+    if (int rc = lg_bind_weights(g.get(), n_floats)) return rc;
     g->n_blob = n_floats;
     {   // split every transformer-layer weight matrix into k-panel fp16 planes (same offsets as the blob)
         auto splitw = [&](const float* w, int N, int K) {
@@ -2584,15 +2583,12 @@ int sslam_lightglue_create_batched(sslam_ctx* ctx, const float* weights, size_t 
         splitw(g->w_in, D, DIN);                               // the input / final projections (lg_proj_big_kernel)
         for (int i = 0; i < NL; ++i) splitw(g->fp_w + (size_t)i * g->fp_stride, D, D);
         int wflag = 0;
-        if (int rc = lg_take_range_flag(g, &wflag)) { g->arena.release(); delete g; return rc; }
-        if (wflag) {
-            g->arena.release(); delete g;
-            SSLAM_REQUIRE(false, "sslam_lightglue_create: a weight with |value| >= 65520 does not fit the fp16 planes of the "
-                                 "split-precision path");
-        }
+        if (int rc = lg_take_range_flag(g.get(), &wflag)) return rc;
+        SSLAM_REQUIRE(!wflag, "sslam_lightglue_create: a weight with |value| >= 65520 does not fit the fp16 planes of the "
+                              "split-precision path");
     }
     sslam::ctx_retain(ctx);
-    *out = g;
+    *out = g.release();
     return 0;
 }
 
@@ -2602,16 +2598,7 @@ int sslam_lightglue_create(sslam_ctx* ctx, const float* weights, size_t n_floats
 }
 
 int sslam_lightglue_destroy(sslam_lightglue* g) {
-    if (!g) return 0;
-    (void)hipStreamSynchronize(g->ctx->stream);
-    g->graphs.clear();
-    for (hipEvent_t e : g->ev) (void)hipEventDestroy(e);
-    if (g->zero_plane) (void)hipFree(g->zero_plane);
-    g->arena.release();
-    sslam_ctx* ctx = g->ctx;
-    delete g;
-    sslam::ctx_release(ctx);
-    return 0;
+    return sslam::destroy_instance(g);
 }
 
 int sslam_lightglue_set_conf(sslam_lightglue* g, float depth_confidence, float width_confidence,

@@ -516,7 +516,7 @@ struct sslam_orb {
     long long cap = 0;                           // output rows any call can produce
     OrbPlan plan{};                              // of the last call (stage_read reads it)
     bool have_plan = false;
-    char* slab = nullptr;
+    sslam::OwnedSlab slab;
     uint8_t *img = nullptr, *blur = nullptr;
     uint32_t *cand_xy = nullptr, *cand_score = nullptr, *cand_key = nullptr;
     unsigned long long* skey = nullptr;
@@ -529,9 +529,21 @@ struct sslam_orb {
 
 namespace {
 
-void orb_free(sslam_orb* o) {
-    if (o->slab) (void)hipFree(o->slab);
-    delete o;
+// the slab-backed pointers of the instance, in slab order; P: the plan of the largest frame
+void orb_bind(sslam_orb* o, const OrbPlan& P, sslam::Slab& S) {
+    const size_t nc = (size_t)o->cap, sb = (size_t)std::max(P.slab_bytes, 256LL);
+    o->img = S.take<uint8_t>(sb);
+    o->blur = S.take<uint8_t>(sb);
+    o->cand_xy = S.take<uint32_t>(nc);
+    o->cand_score = S.take<uint32_t>(nc);
+    o->cand_key = S.take<uint32_t>(nc);
+    o->skey = S.take<unsigned long long>(nc);
+    o->ctl = S.take<OrbCtl>(1);
+    o->pattern = S.take<int8_t>(2 * ORB_PATTERN_POINTS);
+    o->xy = S.take<float>(2 * nc);
+    o->aux = S.take<float>(4 * nc);
+    o->desc = S.take<uint8_t>(32 * nc);
+    o->n = S.take<int32_t>(1);
 }
 
 int orb_enqueue(sslam_orb* o, const uint8_t* img_dev, int h, int w, int c, float* xy, float* aux, uint8_t* desc, int32_t* n_out) {
@@ -597,42 +609,22 @@ extern "C" int sslam_orb_create(sslam_ctx* ctx, int max_w, int max_h, int nfeatu
         orb_default_pattern(pat);
     }
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
-    sslam_orb* o = new sslam_orb;
+    std::unique_ptr<sslam_orb> o(new sslam_orb);
     o->ctx = ctx; o->p = p; o->max_w = max_w; o->max_h = max_h;
     const OrbPlan P = orb_plan(p, max_w, max_h);
     o->cap = orb_capacity(p, max_w, max_h);
-    const size_t nc = (size_t)o->cap, sb = (size_t)std::max(P.slab_bytes, 256LL);
-    sslam::Carver carve;
-    const size_t o_img = carve(sb), o_blur = carve(sb), o_cxy = carve(nc * 4), o_cs = carve(nc * 4), o_ck = carve(nc * 4),
-                 o_sv = carve(nc * 8), o_ctl = carve(sizeof(OrbCtl)), o_pat = carve(sizeof pat), o_xy = carve(nc * 8),
-                 o_aux = carve(nc * 16), o_desc = carve(nc * 32), o_n = carve(sizeof(int32_t));
-    if (const hipError_t e = hipMalloc((void**)&o->slab, carve.bytes); e != hipSuccess) {
-        sslam::set_error("%s: %zu bytes for %dx%d, %d levels: %s", who, carve.bytes, max_w, max_h, nlevels, hipGetErrorString(e));
-        orb_free(o);
-        return 1;
-    }
-    char* b = o->slab;
-    o->img = (uint8_t*)(b + o_img); o->blur = (uint8_t*)(b + o_blur);
-    o->cand_xy = (uint32_t*)(b + o_cxy); o->cand_score = (uint32_t*)(b + o_cs); o->cand_key = (uint32_t*)(b + o_ck);
-    o->skey = (unsigned long long*)(b + o_sv); o->ctl = (OrbCtl*)(b + o_ctl); o->pattern = (int8_t*)(b + o_pat);
-    o->xy = (float*)(b + o_xy); o->aux = (float*)(b + o_aux); o->desc = (uint8_t*)(b + o_desc); o->n = (int32_t*)(b + o_n);
+    if (int rc = o->slab.alloc(who, false, [&](sslam::Slab& S) { orb_bind(o.get(), P, S); })) return rc;
     if (const hipError_t e = hipMemcpy(o->pattern, pat, sizeof pat, hipMemcpyHostToDevice); e != hipSuccess) {
         sslam::set_error("%s: pattern upload: %s", who, hipGetErrorString(e));
-        orb_free(o);
         return 1;
     }
     sslam::ctx_retain(ctx);
-    *out = o;
+    *out = o.release();
     return 0;
 }
 
 extern "C" int sslam_orb_destroy(sslam_orb* o) {
-    if (!o) return 0;
-    (void)hipStreamSynchronize(o->ctx->stream);
-    sslam_ctx* ctx = o->ctx;
-    orb_free(o);
-    sslam::ctx_release(ctx);
-    return 0;
+    return sslam::destroy_instance(o);
 }
 
 extern "C" int sslam_orb_capacity(sslam_orb* o, int* cap) {

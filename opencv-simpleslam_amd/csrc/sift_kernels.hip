@@ -653,7 +653,7 @@ struct sslam_sift {
     SiftPlan plan{};                             // of the last call (stage_read reads it)
     bool have_plan = false;
     SiftTaps taps;
-    char* slab = nullptr;
+    sslam::OwnedSlab slab;
     float *gauss = nullptr, *dog = nullptr, *tmp_a = nullptr, *tmp_b = nullptr, *taps_dev = nullptr;
     int32_t *cand = nullptr, *ref = nullptr, *flag = nullptr, *sticky = nullptr;
     float *hist = nullptr, *rkey = nullptr;
@@ -665,9 +665,27 @@ struct sslam_sift {
 
 namespace {
 
-void sift_free(sslam_sift* o) {
-    if (o->slab) (void)hipFree(o->slab);
-    delete o;
+// the slab-backed pointers of the instance, in slab order; P: the plan of the largest frame
+void sift_bind(sslam_sift* o, const SiftPlan& P, sslam::Slab& S) {
+    const size_t nc = (size_t)o->cand_cap, nk = (size_t)o->kp_cap;
+    o->gauss = S.take<float>((size_t)std::max(P.gauss_floats, 1LL));
+    o->dog = S.take<float>((size_t)std::max(P.dog_floats, 1LL));
+    o->tmp_a = S.take<float>((size_t)P.tmp_floats);
+    o->tmp_b = S.take<float>((size_t)P.tmp_floats);
+    o->taps_dev = S.take<float>(o->taps.taps.size());
+    o->cand = S.take<int32_t>(4 * nc);
+    o->ref = S.take<int32_t>(8 * nc);
+    o->hist = S.take<float>(40 * nc);
+    o->kp = S.take<uint32_t>(8 * nk);
+    o->flag = S.take<int32_t>(nk);
+    o->rkey = S.take<float>(nk);
+    o->ctl = S.take<SiftCtl>(1);
+    o->sticky = S.take<int32_t>(1);
+    o->xy = S.take<float>(2 * nk);
+    o->aux = S.take<float>(3 * nk);
+    o->oct = S.take<int32_t>(nk);
+    o->desc = S.take<float>(SIFT_DESCR_LEN * nk);
+    o->n = S.take<int32_t>(1);
 }
 
 int sift_enqueue(sslam_sift* o, const uint8_t* img_dev, int h, int w, int c, float* xy, float* aux, int32_t* oct, float* desc, int32_t* n_out) {
@@ -746,47 +764,26 @@ extern "C" int sslam_sift_create(sslam_ctx* ctx, int max_w, int max_h, int nfeat
     SSLAM_REQUIRE(max_candidates >= 0 && max_keypoints >= 0, "%s: max_candidates %d / max_keypoints %d is negative (0: the default)", who,
                   max_candidates, max_keypoints);
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
-    sslam_sift* o = new sslam_sift;
+    std::unique_ptr<sslam_sift> o(new sslam_sift);
     o->ctx = ctx; o->p = p; o->max_w = max_w; o->max_h = max_h;
     sift_capacities(p, max_w, max_h, max_candidates, max_keypoints, &o->cand_cap, &o->kp_cap);
     o->taps = sift_taps(p);
     const SiftPlan P = sift_plan(p, max_w, max_h);
-    const size_t nc = (size_t)o->cand_cap, nk = (size_t)o->kp_cap, nt = o->taps.taps.size();
-    sslam::Carver carve;
-    const size_t o_g = carve((size_t)std::max(P.gauss_floats, 1LL) * 4), o_d = carve((size_t)std::max(P.dog_floats, 1LL) * 4),
-                 o_ta = carve((size_t)P.tmp_floats * 4), o_tb = carve((size_t)P.tmp_floats * 4), o_taps = carve(nt * 4), o_c = carve(nc * 16),
-                 o_r = carve(nc * 32), o_h = carve(nc * 160), o_k = carve(nk * 32), o_f = carve(nk * 4), o_rk = carve(nk * 4), o_ctl = carve(sizeof(SiftCtl)),
-                 o_st = carve(4), o_xy = carve(nk * 8), o_aux = carve(nk * 12), o_oct = carve(nk * 4), o_desc = carve(nk * 512), o_n = carve(4);
-    if (const hipError_t e = hipMalloc((void**)&o->slab, carve.bytes); e != hipSuccess) {
-        sslam::set_error("%s: %zu bytes for %dx%d, %d layers: %s", who, carve.bytes, max_w, max_h, n_octave_layers, hipGetErrorString(e));
-        sift_free(o);
-        return 1;
-    }
-    char* b = o->slab;
-    o->gauss = (float*)(b + o_g); o->dog = (float*)(b + o_d); o->tmp_a = (float*)(b + o_ta); o->tmp_b = (float*)(b + o_tb);
-    o->taps_dev = (float*)(b + o_taps); o->cand = (int32_t*)(b + o_c); o->ref = (int32_t*)(b + o_r); o->hist = (float*)(b + o_h);
-    o->kp = (uint32_t*)(b + o_k); o->flag = (int32_t*)(b + o_f); o->rkey = (float*)(b + o_rk); o->ctl = (SiftCtl*)(b + o_ctl); o->sticky = (int32_t*)(b + o_st);
-    o->xy = (float*)(b + o_xy); o->aux = (float*)(b + o_aux); o->oct = (int32_t*)(b + o_oct); o->desc = (float*)(b + o_desc); o->n = (int32_t*)(b + o_n);
-    hipError_t e = hipMemcpy(o->taps_dev, o->taps.taps.data(), nt * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(o->sticky, 0, 4);
+    if (int rc = o->slab.alloc(who, false, [&](sslam::Slab& S) { sift_bind(o.get(), P, S); })) return rc;
+    hipError_t e = hipMemcpy(o->taps_dev, o->taps.taps.data(), o->taps.taps.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(o->sticky, 0, sizeof(int32_t));
     if (e == hipSuccess) e = hipMemset(o->ctl, 0, sizeof(SiftCtl));
     if (e != hipSuccess) {
         sslam::set_error("%s: tap upload: %s", who, hipGetErrorString(e));
-        sift_free(o);
         return 1;
     }
     sslam::ctx_retain(ctx);
-    *out = o;
+    *out = o.release();
     return 0;
 }
 
 extern "C" int sslam_sift_destroy(sslam_sift* o) {
-    if (!o) return 0;
-    (void)hipStreamSynchronize(o->ctx->stream);
-    sslam_ctx* ctx = o->ctx;
-    sift_free(o);
-    sslam::ctx_release(ctx);
-    return 0;
+    return sslam::destroy_instance(o);
 }
 
 extern "C" int sslam_sift_capacity(sslam_sift* o, int* rows, int* candidates) {

@@ -24,6 +24,7 @@
 struct sslam_undistort {
     sslam_ctx* ctx = nullptr;
     int W = 0, H = 0;
+    sslam::OwnedSlab slab;
     float* mapx = nullptr;       // [H*W]
     float* mapy = nullptr;       // [H*W]
     int16_t* ixy = nullptr;      // [H*W][2]
@@ -162,31 +163,18 @@ bool ud_inverse3(const double* m, double* o) {
     return true;
 }
 
-void ud_free(sslam_undistort* u) {
-    if (u->mapx) (void)hipFree(u->mapx);
-    if (u->mapy) (void)hipFree(u->mapy);
-    if (u->ixy) (void)hipFree(u->ixy);
-    if (u->alpha) (void)hipFree(u->alpha);
-    delete u;
-}
-
-// the instance and its four device arrays (sizes in whole 16-byte units: the remap kernel reads records four at a time)
-int ud_alloc(sslam_ctx* ctx, int W, int H, sslam_undistort** out) {
+// the instance and its four device arrays (sizes in whole units of four records: the remap kernel reads records four at a time)
+int ud_alloc(const char* who, sslam_ctx* ctx, int W, int H, std::unique_ptr<sslam_undistort>& u) {
     SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
-    sslam_undistort* u = new sslam_undistort;
+    u.reset(new sslam_undistort);
     u->ctx = ctx; u->W = W; u->H = H;
-    const size_t n = (size_t)W * H, n4 = sslam::align_up(n, 4);
-    hipError_t e = hipMalloc((void**)&u->mapx, n4 * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&u->mapy, n4 * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&u->ixy, n4 * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&u->alpha, n4 * 2);
-    if (e != hipSuccess) {
-        sslam::set_error("sslam_undistort_create: %zu map entries: %s", n, hipGetErrorString(e));
-        ud_free(u);
-        return 1;
-    }
-    *out = u;
-    return 0;
+    const size_t n4 = sslam::align_up((size_t)W * H, 4);
+    return u->slab.alloc(who, false, [&](sslam::Slab& S) {
+        u->mapx = S.take<float>(n4);
+        u->mapy = S.take<float>(n4);
+        u->ixy = S.take<int16_t>(2 * n4);
+        u->alpha = S.take<uint16_t>(n4);
+    });
 }
 
 int ud_quantise(sslam_undistort* u) {
@@ -242,17 +230,15 @@ extern "C" int sslam_undistort_create(sslam_ctx* ctx, const double* K9, const do
             A[3 * r + c] = R9 ? newK9[3 * r] * R9[c] + newK9[3 * r + 1] * R9[3 + c] + newK9[3 * r + 2] * R9[6 + c] : newK9[3 * r + c];
     SSLAM_REQUIRE(ud_inverse3(A, a.ir), "%s: newK R is singular", who);
     a.fx = K9[0]; a.fy = K9[4]; a.cx = K9[2]; a.cy = K9[5];
-    sslam_undistort* u = nullptr;
-    if (int rc = ud_alloc(ctx, W, H, &u)) return rc;
+    std::unique_ptr<sslam_undistort> u;
+    if (int rc = ud_alloc(who, ctx, W, H, u)) return rc;
     a.W = W; a.n = (size_t)W * H; a.mapx = u->mapx; a.mapy = u->mapy;
     (void)hipGetLastError();
     hipLaunchKernelGGL(ud_map_kernel, dim3(ud_blocks(a.n)), dim3(UD_T), 0, ctx->stream, a);
-    int rc = 0;
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess) { sslam::set_error("%s: launch failed: %s", who, hipGetErrorString(e)); rc = 1; }
-    if (!rc) rc = ud_quantise(u);
-    if (rc) { ud_free(u); return rc; }
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) { sslam::set_error("%s: launch failed: %s", who, hipGetErrorString(e)); return 1; }
+    if (int rc = ud_quantise(u.get())) return rc;
     sslam::ctx_retain(ctx);
-    *out = u;
+    *out = u.release();
     return 0;
 }
 
@@ -262,27 +248,20 @@ extern "C" int sslam_undistort_create_from_maps(sslam_ctx* ctx, const float* map
     SSLAM_REQUIRE(ctx != nullptr && out != nullptr, "%s: NULL argument", who);
     SSLAM_REQUIRE(mapx && mapy, "%s: mapx / mapy is NULL", who);
     if (int rc = ud_check_size(who, W, H)) return rc;
-    sslam_undistort* u = nullptr;
-    if (int rc = ud_alloc(ctx, W, H, &u)) return rc;
+    std::unique_ptr<sslam_undistort> u;
+    if (int rc = ud_alloc(who, ctx, W, H, u)) return rc;
     const size_t n = (size_t)W * H;
     hipError_t e = hipMemcpyAsync(u->mapx, mapx, n * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(u->mapy, mapy, n * 4, hipMemcpyHostToDevice, ctx->stream);
-    int rc = 0;
-    if (e != hipSuccess) { sslam::set_error("%s: upload failed: %s", who, hipGetErrorString(e)); rc = 1; }
-    if (!rc) rc = ud_quantise(u);        // (synchronises: the caller's maps have been read when this returns)
-    if (rc) { ud_free(u); return rc; }
+    if (e != hipSuccess) { sslam::set_error("%s: upload failed: %s", who, hipGetErrorString(e)); return 1; }
+    if (int rc = ud_quantise(u.get())) return rc;        // (synchronises: the caller's maps have been read when this returns)
     sslam::ctx_retain(ctx);
-    *out = u;
+    *out = u.release();
     return 0;
 }
 
 extern "C" int sslam_undistort_destroy(sslam_undistort* u) {
-    if (!u) return 0;
-    (void)hipStreamSynchronize(u->ctx->stream);
-    sslam_ctx* ctx = u->ctx;
-    ud_free(u);
-    sslam::ctx_release(ctx);
-    return 0;
+    return sslam::destroy_instance(u);
 }
 
 extern "C" int sslam_undistort_maps_read(sslam_undistort* u, float* mapx, float* mapy, int16_t* ixy, uint16_t* alpha) {
@@ -311,14 +290,12 @@ extern "C" int sslam_undistort_remap_host(sslam_undistort* u, const uint8_t* src
     if (int rc = ud_check_remap(who, u, src, Hs, Ws, C, dst)) return rc;
     SSLAM_HIP_CHECK(hipSetDevice(u->ctx->device));
     const size_t sb = (size_t)Hs * Ws * C, db = (size_t)u->H * u->W * C;
-    sslam::Carver carve;
-    const size_t o_src = carve(sb), o_dst = carve(db);
-    char* b;
-    if (int rc = sslam::ctx_scratch(u->ctx, carve.bytes, &b)) return rc;
+    uint8_t *src_dev = nullptr, *dst_dev = nullptr;
+    if (int rc = sslam::ctx_bind(u->ctx, [&](sslam::Slab& S) { src_dev = S.take<uint8_t>(sb); dst_dev = S.take<uint8_t>(db); })) return rc;
     hipStream_t s = u->ctx->stream;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b + o_src, src, sb, hipMemcpyHostToDevice, s));
-    if (int rc = ud_enqueue_remap(u, (const uint8_t*)(b + o_src), Hs, Ws, C, (uint8_t*)(b + o_dst))) return rc;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(dst, b + o_dst, db, hipMemcpyDeviceToHost, s));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, src_dev, src, sb));
+    if (int rc = ud_enqueue_remap(u, src_dev, Hs, Ws, C, dst_dev)) return rc;
+    SSLAM_HIP_CHECK(sslam::copy_down(s, dst, dst_dev, db));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
     return 0;
 }

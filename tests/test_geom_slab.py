@@ -1,8 +1,9 @@
-"""The geometry entries' slab and chunk schedule (csrc/geom_slab.hpp) on the CPU.  Every geometry entry lays its pieces of
-the context's scratch slab out with Slab::take<T>(count), once to measure and once bound to the slab, and the four RANSAC
-entries take their sample-loop chunks from ransac_chunk_bounds.  This test compiles the header (plain C++17, no HIP) behind a
-small extern "C" shim with the host compiler and compares it with `carver` below: a Python restatement of the byte-offset
-rule the entries used before the header existed (`Carver` of the parent's common.hpp), NOT a transcription of the header."""
+"""The slab and the RANSAC chunk schedule (csrc/geom_slab.hpp) on the CPU.  Every geometry entry lays its pieces of the
+context's scratch slab out with Slab::take<T>(count), once to measure and once bound to the slab - and every instance its own
+memory, through the same rule (OwnedSlab in common.hpp) - and the four RANSAC entries take their sample-loop chunks from
+ransac_chunk_bounds.  This test compiles the header (plain C++17, no HIP) behind a small extern "C" shim with the host compiler
+and compares it with `carver` below: a Python restatement of the byte-offset rule the entries and the ORB / SIFT / KLT
+instances used before they took typed pieces (a `carve(bytes)` per piece, since deleted), NOT a transcription of the header."""
 import ctypes
 import shutil
 import subprocess

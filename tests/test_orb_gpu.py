@@ -209,6 +209,32 @@ def test_one_instance_keeps_no_residue_and_repeats_itself(gpu_ctx):
     o.close()
 
 
+def test_two_instances_of_different_capacity_alternate_on_one_context(gpu_ctx):
+    """An instance lays its memory out from its own capacities.  Two of them (another frame bound, nfeatures and level count:
+    every piece of the two differs in size) alive on one context and called in turn return, each, bit for bit what it returns
+    alone on a fresh context - which is the restatement's.  A pointer left from the measuring pass, a piece sized in another
+    unit than its pointer's, or two pieces that overlap would show here."""
+    native = load_pkg("_native")
+    specs = [(dict(max_h=MAXH, max_w=MAXW), dict(nfeatures=60, nlevels=3), ()),          # (the frame at its default size)
+             (dict(max_h=80, max_w=100), dict(nfeatures=300, nlevels=8), (80, 100))]    # two stored levels of eight
+    alone = []
+    for cap, kw, size in specs:
+        ctx = native.Context(0)
+        o = make(ctx, **cap, **kw)
+        alone.append(o.detect_arrays(S.image("mosaic", *size)))
+        o.close(); ctx.close()
+        assert_same_output(alone[-1], S.reference("mosaic", *size, **kw))
+        assert len(set(alone[-1][1][:, 3].tolist())) > 1                     # keypoints on more than one level
+    both = [make(gpu_ctx, **cap, **kw) for cap, kw, _ in specs]
+    for _ in range(2):                                                       # (the first call creates the native instance)
+        for o, (_, _, size), want in zip(both, specs, alone):
+            for x, y in zip(o.detect_arrays(S.image("mosaic", *size)), want):
+                assert x.tobytes() == y.tobytes()
+    assert both[0].capacity != both[1].capacity
+    for o in both:
+        o.close()
+
+
 def test_the_device_entry_and_the_chain_into_the_matcher_and_the_f_filter(gpu_ctx):
     """ORB -> sslam_bf_match_dev (device counts) -> sslam_fmat_ransac_dev on a shifted pair, nothing read back in between,
     equals the same chain fed from host arrays."""

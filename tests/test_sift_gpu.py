@@ -115,6 +115,36 @@ def test_two_runs_are_identical_and_a_larger_instance_changes_nothing(gpu_ctx):
     a.close(); b.close()
 
 
+def test_two_instances_of_different_capacity_alternate_on_one_context(gpu_ctx):
+    """An instance lays its memory out from its own capacities.  Two of them (another frame bound, nfeatures, and candidate and
+    keypoint capacities that are exactly the small frame's counts: every piece of the two differs in size) alive on one context
+    and called in turn return, each, bit for bit what it returns alone on a fresh context - which is the restatement's.  A
+    pointer left from the measuring pass, a piece sized in another unit than its pointer's, or two pieces that overlap would
+    show here."""
+    native = load_pkg("_native")
+    small = S.reference("mosaic", S.HS, S.WS)
+    specs = [(dict(nfeatures=40), (S.H, S.W)),
+             (dict(max_h=S.HS, max_w=S.WS, max_candidates=sum(len(c) for c in small["cand"]), max_keypoints=small["n_raw"]), (S.HS, S.WS))]
+    alone = []
+    for kw, size in specs:
+        ctx = native.Context(0)
+        o = make(ctx, **kw)
+        alone.append(o.detect_arrays(S.image("mosaic", *size)))
+        o.close(); ctx.close()
+        assert len(set((alone[-1][2] & 255).tolist())) > 1                   # keypoints in more than one octave
+    assert_same_output(alone[0], S.reference("mosaic", S.H, S.W, nfeatures=40))
+    assert_same_output(alone[1], small)
+    both = [make(gpu_ctx, **kw) for kw, _ in specs]
+    for _ in range(2):                                                       # (the first call creates the native instance)
+        for o, (_, size), want in zip(both, specs, alone):
+            for x, y in zip(o.detect_arrays(S.image("mosaic", *size)), want):
+                assert x.tobytes() == y.tobytes()
+            assert o.overflow() == 0
+    assert both[0].capacity != both[1].capacity and both[0].candidate_capacity != both[1].candidate_capacity
+    for o in both:
+        o.close()
+
+
 def test_a_frame_beyond_a_capacity_is_voided_not_truncated(gpu_ctx):
     N = load_pkg("_native")
     ref = S.reference("mosaic")
