@@ -311,8 +311,13 @@ def reproj_err(pts3d32, pts2d32, rvec, tvec, K):
 
 
 # ---- EPnP -----------------------------------------------------------------------------------------------------------
-def epnp(pw32, ip32, K):
-    """solvePnP(SOLVEPNP_EPNP): (R [3,3], t [3]).  pw32 [m,3], ip32 [m,2] float32."""
+def epnp(pw32, ip32, K, trace=None):
+    """solvePnP(SOLVEPNP_EPNP): (R [3,3], t [3]).  pw32 [m,3], ip32 [m,2] float32.
+    `trace` (a dict, tests only; no result depends on it) receives the branches taken: `beta` (which of the three
+    approximations won), per approximation `flip` (solve_for_sign negated the points) and `det_neg` (the row flip of
+    estimate_R_and_t), `dropped_axes` (control axes left out of the pseudo-inverse), `ls_singular` / `gn_singular`
+    (qr_solve calls that met a zero column, in the beta least squares / in Gauss-Newton)."""
+    tr = {"beta": -1, "flip": [], "det_neg": [], "dropped_axes": 0, "ls_singular": 0, "gn_singular": 0}
     fu, fv, uc, vc = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
     m = len(pw32)
     pws = pw32.astype(np.float64)
@@ -343,6 +348,8 @@ def epnp(pw32, ip32, K):
     for j in range(3):
         if ks[j] > thr:
             ci[j] = uct[j] / ks[j]
+        else:
+            tr["dropped_axes"] += 1
     alphas = np.zeros((m, 4))
     for i in range(m):
         d = pws[i] - cws[0]
@@ -395,11 +402,15 @@ def epnp(pw32, ip32, K):
             X = qr_solve(A, bb)
             if X is not None:
                 x = X
+            else:
+                tr["gn_singular"] += 1
             betas = [betas[i] + x[i] for i in range(4)]
         return betas
 
     def ls(cols):
         X = qr_solve(L[:, cols], rho)
+        if X is None:
+            tr["ls_singular"] += 1
         return np.zeros(len(cols)) if X is None else X
 
     with np.errstate(all="ignore"):
@@ -428,7 +439,7 @@ def epnp(pw32, ip32, K):
         B3 += [_div(b5[3], B3[0]), 0.0]
 
         best = None
-        for betas in (B1, B2, B3):
+        for which, betas in enumerate((B1, B2, B3)):
             betas = gauss_newton(betas)
             ccs = np.zeros((4, 3))
             for i in range(4):
@@ -441,6 +452,7 @@ def epnp(pw32, ip32, K):
                 a = alphas[i]
                 for j in range(3):
                     pcs[i, j] = a[0] * ccs[0, j] + a[1] * ccs[1, j] + a[2] * ccs[2, j] + a[3] * ccs[3, j]
+            tr["flip"].append(bool(pcs[0, 2] < 0.0))
             if pcs[0, 2] < 0.0:
                 ccs, pcs = -ccs, -pcs
             pc0, pw0 = np.zeros(3), np.zeros(3)
@@ -458,6 +470,7 @@ def epnp(pw32, ip32, K):
             R = polar3(abt)
             det = (R[0, 0] * R[1, 1] * R[2, 2] + R[0, 1] * R[1, 2] * R[2, 0] + R[0, 2] * R[1, 0] * R[2, 1]
                    - R[0, 2] * R[1, 1] * R[2, 0] - R[0, 1] * R[1, 0] * R[2, 2] - R[0, 0] * R[1, 2] * R[2, 1])
+            tr["det_neg"].append(bool(det < 0))
             if det < 0:
                 R[2] = -R[2]
             t = np.array([pc0[j] - dot(R[j], pw0) for j in range(3)])
@@ -473,13 +486,19 @@ def epnp(pw32, ip32, K):
             err = sum2 / m
             if best is None or err < best[0]:
                 best = (err, R, t)
+                tr["beta"] = which
+    if trace is not None:
+        trace.update(tr)
     return best[1], best[2]
 
 
-def epnp_model(pw32, ip32, K):
-    """runKernel: the EPnP pose as the callback's (rvec, tvec)."""
-    R, t = epnp(pw32, ip32, K)
-    if not np.all(np.isfinite(R)) or not np.all(np.isfinite(t)):
+def epnp_model(pw32, ip32, K, trace=None):
+    """runKernel: the EPnP pose as the callback's (rvec, tvec).  `trace`: epnp's, plus `nan_model`."""
+    R, t = epnp(pw32, ip32, K, trace)
+    finite = bool(np.all(np.isfinite(R)) and np.all(np.isfinite(t)))
+    if trace is not None:
+        trace["nan_model"] = not finite
+    if not finite:
         return np.full(3, np.nan), np.full(3, np.nan)
     return rodrigues_R2r(R), t
 
@@ -519,8 +538,18 @@ def _project_err(X, m, param, K):
     return err
 
 
-def refine_lm(X, m, rvec, tvec, K, max_iter=LM_MAX_ITERS):
-    """CvLevMarq driven as cvFindExtrinsicCameraParams2 drives it.  Returns (rvec, tvec, iterations)."""
+def refine_lm(X, m, rvec, tvec, K, max_iter=LM_MAX_ITERS, trace=None):
+    """CvLevMarq driven as cvFindExtrinsicCameraParams2 drives it.  Returns (rvec, tvec, iterations).
+    `trace` (a dict, tests only) receives `rejected` (steps retried with a larger lambda), `k_max`, `exit` ("cap": the
+    iteration limit, "small_step": the relative step), `min_margin` (the smallest |err_norm - prev| / prev over the
+    accept / reject decisions; nan compares as 0) and `stop_margin` (the smallest |step - FLT_EPSILON| / FLT_EPSILON
+    over the stop tests that the step decided)."""
+    tr = {"rejected": 0, "k_max": -3, "exit": None, "min_margin": math.inf, "stop_margin": math.inf}
+
+    def _margin(a, b):
+        with np.errstate(all="ignore"):
+            v = abs(a - b) / b if b != 0 else math.inf
+        return 0.0 if v != v else float(v)
     param = np.concatenate([np.asarray(rvec, np.float64), np.asarray(tvec, np.float64)])
     k = -3
     iters = 0
@@ -541,9 +570,12 @@ def refine_lm(X, m, rvec, tvec, K, max_iter=LM_MAX_ITERS):
         param = step()
         while True:
             err_norm = float(np.sqrt(np.sum(_project_err(X, m, param, K) ** 2)))
+            tr["min_margin"] = min(tr["min_margin"], _margin(err_norm, prev_err_norm))
             if err_norm > prev_err_norm:
                 k += 1
+                tr["k_max"] = max(tr["k_max"], k)
                 if k <= 16:
+                    tr["rejected"] += 1
                     param = step()
                     continue
             break
@@ -551,16 +583,28 @@ def refine_lm(X, m, rvec, tvec, K, max_iter=LM_MAX_ITERS):
         iters += 1
         dn = float(np.sqrt(np.sum((param - prev) ** 2)))
         pn = float(np.sqrt(np.sum(prev ** 2)))
+        if iters < max_iter:
+            tr["stop_margin"] = min(tr["stop_margin"], _margin(dn / (pn + DBL_EPSILON), FLT_EPSILON))
         if iters >= max_iter or dn / (pn + DBL_EPSILON) < FLT_EPSILON:
+            tr["exit"] = "cap" if iters >= max_iter else "small_step"
             break
         prev_err_norm = err_norm
         err, J = _project_jac(X, m, param, K)
+    if trace is not None:
+        trace.update(tr)
     return param[:3].copy(), param[3:].copy(), iters
 
 
 # ---- solvePnPRansac -------------------------------------------------------------------------------------------------
-def solve_pnp_ransac(pts3d, pts2d, K, ransac_px=8.0, use_guess=False, iters=100, conf=0.99):
-    """Returns (ok, rvec, tvec, mask bool[n], info dict).  info: inliers (-1: no model), samples, winner, lm_iters."""
+def solve_pnp_ransac(pts3d, pts2d, K, ransac_px=8.0, use_guess=False, iters=100, conf=0.99, trace=None):
+    """Returns (ok, rvec, tvec, mask bool[n], info dict).  info: inliers (-1: no model), samples, winner, lm_iters.
+    `trace` (a dict, tests only) receives `samples` (one epnp_model trace per sample, with its subset `idx`, its
+    `model` and its inlier count `good`), `budgets` (the budget after each new best), `winner` / `last` (the models
+    the refinement may start from) and `lm` (refine_lm's trace)."""
+    tr = {"samples": [], "budgets": [], "winner": None, "last": None, "lm": {}}
+    if trace is not None:
+        trace.update(tr)
+        tr = trace
     p3 = np.ascontiguousarray(pts3d, np.float32).reshape(-1, 3)
     p2 = np.ascontiguousarray(pts2d, np.float32).reshape(-1, 2)
     K = np.asarray(K, np.float64).reshape(3, 3)
@@ -571,7 +615,9 @@ def solve_pnp_ransac(pts3d, pts2d, K, ransac_px=8.0, use_guess=False, iters=100,
             raise NotImplementedError("npoints == 4: OpenCV's P3P minimal solver is not restated")
         return False, None, None, np.zeros(n, bool), info
     if n == MODEL_POINTS:
-        rvec, tvec = epnp_model(p3, p2, K)
+        st = {"idx": list(range(n))}
+        rvec, tvec = epnp_model(p3, p2, K, st)
+        tr["samples"].append(st)
         info.update(inliers=n)
         return True, rvec, tvec, np.ones(n, bool), info
     thresh = float(np.float32(ransac_px))
@@ -588,24 +634,29 @@ def solve_pnp_ransac(pts3d, pts2d, K, ransac_px=8.0, use_guess=False, iters=100,
             while v in idx:
                 v = rng.uniform(0, n)
             idx.append(v)
-        model = epnp_model(p3[idx], p2[idx], K)
+        st = {"idx": idx}
+        model = epnp_model(p3[idx], p2[idx], K, st)
+        tr["samples"].append(st)
         last = model
         e = reproj_err(p3, p2, model[0], model[1], K)
         mask = e <= t
         good = int(np.count_nonzero(mask))
+        st["model"], st["good"] = model, good
         if good > max(max_good, MODEL_POINTS - 1):
             max_good, best, best_mask = good, model, mask
             info["sample"] = it
             niters = update_num_iters(conf, (n - good) / n, MODEL_POINTS, niters)
+            tr["budgets"].append(niters)
         it += 1
     info["samples"] = it
     if best is None:
         return False, None, None, np.zeros(n, bool), info
     info["inliers"] = max_good
     start = last if use_guess else best
+    tr["winner"], tr["last"] = best, last
     X = p3[best_mask].astype(np.float64)
     m = p2[best_mask].astype(np.float64)
-    rvec, tvec, lm_iters = refine_lm(X, m, start[0], start[1], K)
+    rvec, tvec, lm_iters = refine_lm(X, m, start[0], start[1], K, trace=tr["lm"])
     info["lm_iters"] = lm_iters
     return True, rvec, tvec, best_mask, info
 

@@ -41,6 +41,8 @@ def _compare(PN, sc, use_guess, iters=S.ITERS):
     assert near.sum() <= 1
     np.testing.assert_array_equal(gmask[~near], mask[~near])
     assert ginfo["inliers"] == int(gmask.sum())
+    if not near.any():
+        assert ginfo["inliers"] == info["inliers"]
     Tr = O.pose_matrix(r, t)
     assert S.rot_err_rad(T[:3, :3], Tr[:3, :3]) < 1e-6
     assert np.linalg.norm(T[:3, 3] - Tr[:3, 3]) < 1e-6 * (1 + np.linalg.norm(Tr[:3, 3]))
