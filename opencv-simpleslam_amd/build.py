@@ -76,8 +76,7 @@ def _build_asm_kernels(obj_dir: Path, force: bool, verbose: bool):
         key = _digest(clang, lld, ARCH, *[g_.read_bytes() for g_ in sorted(CSRC.glob("gen_*.py"))])     # (a generator may run another)
         if force or not obj.exists() or not keyf.exists() or keyf.read_text().strip() != key:
             keyf.unlink(missing_ok=True)
-            env = {k: v for k, v in os.environ.items() if not k.startswith("ATTN_ASM_")}     # no experiment switches
-            text = subprocess.run([sys.executable, str(gen)], capture_output=True, text=True, env=env)
+            text = subprocess.run([sys.executable, str(gen)], capture_output=True, text=True)
             if text.returncode != 0:
                 raise RuntimeError(f"{gen.name} failed:\n{text.stderr}")
             asm, dev_o, hsaco, stub = (obj_dir / f"{name}{e}" for e in (".s", ".dev.o", ".hsaco", "_stub.s"))

@@ -13,7 +13,6 @@ echo "== N=1900 ragged cross"; ATTN_PP=4 ATTN_CMP=1 ATTN_CROSS=1 ATTN_N1=1333 ti
 echo "== N=200 N1=17 cross";   ATTN_PP=4 ATTN_CMP=1 ATTN_CROSS=1 ATTN_N1=17 timeout -k 5 60 /tmp/attn_b 200 1 1 1 | tail -4 || exit 1
 echo "== N=64 self";           ATTN_PP=4 ATTN_CMP=1 timeout -k 5 60 /tmp/attn_b 64 3 1 1 | tail -4 || exit 1
 for rep in 1 2; do
-  echo -n "[asm pk] "; ATTN_ASM_PK=1 python3 opencv-simpleslam_amd/csrc/gen_lg_attention_asm.py > /tmp/p.s; /opt/rocm/lib/llvm/bin/clang -x assembler -target amdgcn-amd-amdhsa -mcpu=gfx950 -c /tmp/p.s -o /tmp/p.o; /opt/rocm/lib/llvm/bin/ld.lld -shared /tmp/p.o -o /tmp/p.hsaco; ATTN_HSACO=/tmp/p.hsaco ATTN_PP=4 timeout -k 5 120 /tmp/attn_b 2048 8 1 5
   echo -n "[hs ] "; ATTN_PP=3 timeout -k 5 120 /tmp/attn_b 2048 8 1 5
   echo -n "[asm] "; ATTN_PP=4 timeout -k 5 120 /tmp/attn_b 2048 8 1 5
 done

@@ -1,4 +1,6 @@
 # MFMA-only stream of the hand-scheduled attention kernel: does the distance between dependent MFMAs matter?
+# RECORD (profiles/r03_attention_experiments.md, r03_attn_asm_abl*.log): needs the tree of commit 687900d (the last one whose generator
+# read ATTN_ASM_* switches); on later sources the variable it sets selects nothing and every leg times the product kernel.
 cd $GRAFT_REPO_ROOT
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I opencv-simpleslam_amd/csrc scripts/ubench/attn_bench.hip -o /tmp/attn_b 2>/dev/null
 for abl in novalu,nods,nodma novalu,nods,nodma,qk3acc novalu,nods,nodma,qkchain novalu,qk3acc novalu; do

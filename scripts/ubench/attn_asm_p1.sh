@@ -1,5 +1,7 @@
 # r04: what the P-one-plane instruction stream would take (profiles/r04_split_study.md): the assembly kernel built with
 # ATTN_ASM_P1=1 (20 MFMAs per sub-step, no P.lo arithmetic; results are NOT valid) against the product kernel, same box
+# RECORD: needs the tree of commit 687900d (the last one whose generator read ATTN_ASM_* switches).  That stream has since become the
+# kernel of the opt-in precision: csrc/gen_lg_attention_asm_p1.py prints it, under the name lg_attention_asm_p1_kernel.
 cd $GRAFT_REPO_ROOT
 set -e
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I opencv-simpleslam_amd/csrc scripts/ubench/attn_bench.hip -o /tmp/attn_b 2>/dev/null

@@ -1,4 +1,6 @@
 # SQ counters + effective clock of the attention kernels in the stand-alone bench (hs, asm, asm MFMA-only)
+# RECORD (profiles/r03_attention_experiments.md, r03_attn_asm_pmc.log): needs the tree of commit 687900d (the last one whose generator
+# read ATTN_ASM_* switches); on later sources the variable it sets selects nothing and every code object is the product kernel.
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I opencv-simpleslam_amd/csrc scripts/ubench/attn_bench.hip -o /tmp/attn_b 2>/dev/null

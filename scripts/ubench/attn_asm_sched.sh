@@ -1,4 +1,6 @@
 # schedule knobs of the hand-scheduled attention kernel: bitwise check + timing per configuration (DEFER NEXP_ODD WEIGHTED)
+# RECORD (profiles/r03_attention_experiments.md, the variants table): needs the tree of commit 687900d (the last one whose generator
+# read ATTN_ASM_* switches); on later sources the variables it sets select nothing and every configuration is the product kernel.
 cd $GRAFT_REPO_ROOT
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I opencv-simpleslam_amd/csrc scripts/ubench/attn_bench.hip -o /tmp/attn_b 2>/dev/null
 for rep in 1 2; do
