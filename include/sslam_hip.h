@@ -402,6 +402,36 @@ int sslam_reproject_match_dev(sslam_ctx* ctx, int n_points, const double* pts3d,
                               int img_w, int img_h, double radius_px, double max_dist,
                               int32_t* kp_of_point, float* uv_out, int32_t* info_out);
 
+/* The Hamming branch of the same function for binary descriptors (`des_cur.dtype == np.uint8`: ORB 32 bytes,
+ * AKAZE 61): `_desc_distance` (:78-112) takes cv2.norm(a, b, NORM_HAMMING), the threshold is `max_hamm`.
+ * Projection, radius search and the greedy pass are the float entries'; only the pair score differs: the
+ * minimum over the point's stored rows of popcount(obs ^ des), exact.
+ *   obs_desc_u8[n_points*6*64] uint8: the `desc_bytes`-wide rows among the point's last six observations,
+ *     valid ones first, every row zero from desc_bytes to 64;  obs_cnt as above
+ *   des_u8[n_kp*desc_bytes] contiguous rows (what sslam_orb_detect_* writes as desc);  desc_bytes 2..64
+ *   max_hamm: a decision with best distance == max_hamm is accepted (the reference rejects `best_d > thr`)
+ *   Equal minima: the LOWEST keypoint index wins.  The reference takes the first in cKDTree's traversal
+ *   order, which is unspecified; the two can differ only on a decision that is accepted and tied.
+ *   The other arguments, the status and info_out are those of sslam_reproject_match_host. */
+int sslam_reproject_match_hamming_host(sslam_ctx* ctx, int n_points, const double* pts3d,
+                                       const int32_t* obs_cnt, const uint8_t* obs_desc_u8,
+                                       const double* K9, const double* Tcw16, int n_kp,
+                                       const float* kp_xy, const uint8_t* des_u8, int desc_bytes,
+                                       int img_w, int img_h, double radius_px, double max_hamm,
+                                       int32_t* kp_of_point, float* uv_out, int32_t* info_out);
+
+/* Device-resident variant (enqueue only), as sslam_reproject_match_dev; obs_desc_u8 16-byte aligned.
+ *   n_kp_dev (may be NULL): device int32, the keypoint count a detector left (sslam_orb_detect_dev's
+ *   n_out); clamped to [0, n_kp] and read by the kernels, so no synchronisation between detector and
+ *   association.  Rows at and beyond the count are never matched. */
+int sslam_reproject_match_hamming_dev(sslam_ctx* ctx, int n_points, const double* pts3d,
+                                      const int32_t* obs_cnt, const uint8_t* obs_desc_u8,
+                                      const double* K9, const double* Tcw16, int n_kp,
+                                      const float* kp_xy, const uint8_t* des_u8, int desc_bytes,
+                                      int img_w, int img_h, double radius_px, double max_hamm,
+                                      int32_t* kp_of_point, float* uv_out, int32_t* info_out,
+                                      const int32_t* n_kp_dev);
+
 /* ------------------------------------------------------- brute-force matcher
  * Replaces `cv2.BFMatcher(norm, crossCheck).match(des0, des1)` as `feature_matcher` calls it on the OpenCV branch
  * (slam/core/features_utils.py:173-178; the matcher is built at :54-55 with NORM_HAMMING for ORB / AKAZE, NORM_L2 for

@@ -90,6 +90,10 @@ def _signatures():
                                              vp, vp, vp]),
         "sslam_reproject_match_dev": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, C.c_double, C.c_double,
                                             vp, vp, vp]),
+        "sslam_reproject_match_hamming_host": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double,
+                                                     C.c_double, vp, vp, vp]),
+        "sslam_reproject_match_hamming_dev": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double,
+                                                    C.c_double, vp, vp, vp, vp]),
         "sslam_bf_match_host": (i32, [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp]),
         "sslam_bf_match_dev": (i32, [vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]),
         "sslam_orb_create": (i32, [vp, i32, i32, i32, C.c_double, i32, i32, i32, i32, vp, c_void_pp]),

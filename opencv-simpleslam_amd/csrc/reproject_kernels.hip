@@ -12,12 +12,20 @@
 // them the minimum L2 distance to the point's last <= 6 observation descriptors (float32), one
 // wave per point; (3) one lane then replays the greedy pass over the stored (keypoint, distance)
 // lists in map order.  HBM-bound: Q x 6 x 512 B of observation descriptors read once.
+//
+// Binary descriptors (`uint8` rows: ORB 32 bytes, AKAZE 61) take the same steps (1) and (3); step (2) scores with the
+// Hamming distance (`_desc_distance` :78-112 -> cv2.norm(a, b, NORM_HAMMING)) in `rp_pairs_hamming_kernel`: one LANE per
+// keypoint in range (two passes cover the 128), the point's observation rows read once per wave through uniform
+// addresses, popcount of the XOR, no cross-lane step.  The distance is stored as an exact float (<= 512), so the greedy
+// pass serves both forms.  Equal minima: the lowest keypoint index wins (ascending lists + the strict `<` below).
+// HBM-bound: Q x 6 x 64 B of observation rows read once plus the gathered frame rows (N x B bytes, cache resident).
 #include "common.hpp"
 
 namespace {
 
 constexpr int RP_MAXC = 128;      // keypoints kept per map point (within radius)
 constexpr int RP_DIM = 128;
+constexpr int RP_HB = 64;         // bytes of a stored binary observation row (zero beyond the descriptor's width)
 
 struct RMArgs {
     int Q, N, img_w, img_h;
@@ -29,6 +37,10 @@ struct RMArgs {
     const double* Tcw;            // [16]
     const float* kp;              // [N][2]
     const float* des;             // [N][128]
+    const int32_t* n_kp_dev;      // device count of keypoint rows, clamped to [0, N]; may be NULL (then N)
+    const uint8_t* obs_u8;        // Hamming form: [Q][6][RP_HB], the valid ones first, zero beyond B bytes
+    const uint8_t* des_u8;        // Hamming form: [N][B] contiguous
+    int B;                        // Hamming form: bytes per descriptor row, 2..RP_HB
     float* uv;                    // [Q][2]
     int32_t* cand_n;              // [Q]  (-1: not a candidate)
     int32_t* cand_kp;             // [Q][RP_MAXC]
@@ -37,12 +49,10 @@ struct RMArgs {
     int32_t* info;                // [0] matches, [1] overflow flag, [2] candidates
 };
 
-// one wave per map point: project, collect the keypoints in range (ascending index), score them
-__global__ __launch_bounds__(256) void rp_pairs_kernel(RMArgs a) {
-    __shared__ int list[4][RP_MAXC];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int q = blockIdx.x * 4 + wave;
-    if (q >= a.Q) return;
+// The part both scoring kernels share, one wave per map point q: project, decide whether the point is a candidate, collect
+// the keypoints in range into `list` (LDS, ascending index).  -> the number kept (<= RP_MAXC, overflow flagged), -1 when the
+// point is no candidate (cand_n[q] is then already written).  The wave's LDS writes are complete on return.
+__device__ __forceinline__ int rp_project_collect(const RMArgs& a, int q, int lane, int* list) {
     // `_project_points`: Xc = p R^T + t (float64), uv = (K (Xc / z))[:2] as float32, -1 where z <= 1e-8
     const double px = a.pts[3 * q], py = a.pts[3 * q + 1], pz = a.pts[3 * q + 2];
     const double* T = a.Tcw;
@@ -57,26 +67,38 @@ __global__ __launch_bounds__(256) void rp_pairs_kernel(RMArgs a) {
     }
     const bool cand = zc > 0.0 && u >= 0.0f && u < (float)a.img_w && v >= 0.0f && v < (float)a.img_h && a.obs_cnt[q] > 0;
     if (lane == 0) { a.uv[2 * q] = u; a.uv[2 * q + 1] = v; a.kp_of_point[q] = -1; }
-    if (!cand) { if (lane == 0) a.cand_n[q] = -1; return; }
+    if (!cand) { if (lane == 0) a.cand_n[q] = -1; return -1; }
     // radius search, ascending keypoint index (ballot compaction)
+    const int N = a.n_kp_dev ? min(max(a.n_kp_dev[0], 0), a.N) : a.N;
     int n = 0;
-    for (int base = 0; base < a.N; base += 64) {
+    for (int base = 0; base < N; base += 64) {
         const int i = base + lane;
         bool in = false;
-        if (i < a.N) {
+        if (i < N) {
             const double dx = (double)a.kp[2 * i] - (double)u, dy = (double)a.kp[2 * i + 1] - (double)v;
             in = dx * dx + dy * dy <= a.radius2;
         }
         const unsigned long long m = __ballot(in);
         if (in) {
             const int pos = n + __popcll(m & ((1ull << lane) - 1ull));
-            if (pos < RP_MAXC) list[wave][pos] = i;
+            if (pos < RP_MAXC) list[pos] = i;
         }
         n += __popcll(m);
     }
     if (n > RP_MAXC) { if (lane == 0) atomicOr(&a.info[1], 1); n = RP_MAXC; }
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
+    return n;
+}
+
+// one wave per map point: project, collect the keypoints in range (ascending index), score them
+__global__ __launch_bounds__(256) void rp_pairs_kernel(RMArgs a) {
+    __shared__ int list[4][RP_MAXC];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = blockIdx.x * 4 + wave;
+    if (q >= a.Q) return;
+    const int n = rp_project_collect(a, q, lane, list[wave]);
+    if (n < 0) return;
     // min over the stored observation descriptors of |obs - des|_2 (float32), lane = 2 dimensions
     const int cnt = a.obs_cnt[q];
     float2 o[6];
@@ -93,6 +115,73 @@ __global__ __launch_bounds__(256) void rp_pairs_kernel(RMArgs a) {
             best = fminf(best, sqrtf(s));
         }
         if (lane == 0) { a.cand_kp[(size_t)q * RP_MAXC + c] = i; a.cand_d[(size_t)q * RP_MAXC + c] = best; }
+    }
+    if (lane == 0) a.cand_n[q] = n;
+}
+
+// 16 bytes [16 k, 16 k + 16) of a frame row of B bytes as four little-endian words, zero beyond B.  VEC is the widest load the
+// row layout allows (the host chooses): 16 - B % 16 == 0 and a 16-byte aligned base; 4 - B % 4 == 0 and a 4-byte aligned
+// base; 1 - bytes (AKAZE's 61), which never touches a byte beyond the row.
+template <int VEC>
+__device__ __forceinline__ uint4 rp_row_chunk(const uint8_t* row, int B, int k) {
+    if constexpr (VEC == 16) {
+        return *reinterpret_cast<const uint4*>(row + 16 * k);
+    } else {
+        uint32_t w[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int o = 16 * k + 4 * t;
+            w[t] = 0u;
+            if constexpr (VEC == 4) {
+                if (o < B) w[t] = *reinterpret_cast<const uint32_t*>(row + o);
+            } else {
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    if (o + b < B) w[t] |= (uint32_t)row[o + b] << (8 * b);
+            }
+        }
+        return make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+// The Hamming form of rp_pairs_kernel: the same front, then one LANE per keypoint in range.  A lane holds its keypoint's row
+// chunk by chunk; the point's observation rows have wave-uniform addresses (q through readfirstlane), so they are read once
+// per wave, not per lane; min_j popcount(obs_j ^ des_i) needs no cross-lane step.
+template <int VEC>
+__global__ __launch_bounds__(256) void rp_pairs_hamming_kernel(RMArgs a) {
+    __shared__ int list[4][RP_MAXC];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int q = blockIdx.x * 4 + wave;
+    if (q >= a.Q) return;
+    const int n = rp_project_collect(a, q, lane, list[wave]);
+    if (n < 0) return;
+    const int cnt = min(__builtin_amdgcn_readfirstlane(a.obs_cnt[q]), 6);
+    const int chunks = (a.B + 15) >> 4;
+    const uint4* obs = reinterpret_cast<const uint4*>(a.obs_u8 + (size_t)q * 6 * RP_HB);
+    for (int c0 = 0; c0 < n; c0 += 64) {
+        const int c = c0 + lane;
+        if (c < n) {
+            const int i = list[wave][c];
+            const uint8_t* row = a.des_u8 + (size_t)i * a.B;
+            int acc[6] = {0, 0, 0, 0, 0, 0};
+            for (int k = 0; k < chunks; ++k) {
+                const uint4 d = rp_row_chunk<VEC>(row, a.B, k);
+#pragma unroll
+                for (int j = 0; j < 6; ++j) {
+                    if (j < cnt) {
+                        const uint4 o = obs[j * (RP_HB / 16) + k];
+                        acc[j] += __popcll(((unsigned long long)(o.x ^ d.x) << 32) | (o.y ^ d.y))
+                                + __popcll(((unsigned long long)(o.z ^ d.z) << 32) | (o.w ^ d.w));
+                    }
+                }
+            }
+            int best = acc[0];
+#pragma unroll
+            for (int j = 1; j < 6; ++j)
+                if (j < cnt) best = min(best, acc[j]);
+            a.cand_kp[(size_t)q * RP_MAXC + c] = i;
+            a.cand_d[(size_t)q * RP_MAXC + c] = (float)best;
+        }
     }
     if (lane == 0) a.cand_n[q] = n;
 }
@@ -130,13 +219,15 @@ __global__ __launch_bounds__(64) void rp_assign_kernel(RMArgs a) {
 namespace {
 
 // the slab-backed pointers of RMArgs, in slab order.  host_inputs: the map and keypoint arrays are the slab's too
-void rm_bind(sslam::Slab& sl, RMArgs& a, size_t Q, size_t N, bool host_inputs) {
+// B: 0 for float descriptors, the row width in bytes for the Hamming form
+void rm_bind(sslam::Slab& sl, RMArgs& a, size_t Q, size_t N, bool host_inputs, size_t B = 0) {
     a.K = sl.take<double>(9); a.Tcw = sl.take<double>(16); a.uv = sl.take<float>(Q * 2); a.cand_n = sl.take<int32_t>(Q);
     a.cand_kp = sl.take<int32_t>(Q * RP_MAXC); a.cand_d = sl.take<float>(Q * RP_MAXC);
     a.kp_of_point = sl.take<int32_t>(Q); a.info = sl.take<int32_t>(4);
     if (!host_inputs) return;
-    a.pts = sl.take<double>(Q * 3); a.obs_cnt = sl.take<int32_t>(Q); a.obs_desc = sl.take<float>(Q * 6 * RP_DIM);
-    a.kp = sl.take<float>(N * 2); a.des = sl.take<float>(N * RP_DIM);
+    a.pts = sl.take<double>(Q * 3); a.obs_cnt = sl.take<int32_t>(Q); a.kp = sl.take<float>(N * 2);
+    if (B) { a.obs_u8 = sl.take<uint8_t>(Q * 6 * RP_HB); a.des_u8 = sl.take<uint8_t>(N * B); }
+    else { a.obs_desc = sl.take<float>(Q * 6 * RP_DIM); a.des = sl.take<float>(N * RP_DIM); }
 }
 
 // enqueue the two kernels on device-resident inputs (`a`: every pointer set); K9 / Tcw16 are host values
@@ -148,7 +239,15 @@ int rm_enqueue(sslam_ctx* ctx, RMArgs a, const double* K9, const double* Tcw16, 
     SSLAM_HIP_CHECK(sslam::copy_up(s, a.Tcw, Tcw16, 16));
     SSLAM_HIP_CHECK(hipMemsetAsync(a.info, 0, 16, s));
     a.img_w = img_w; a.img_h = img_h; a.radius2 = radius_px * radius_px; a.thr = max_dist;
-    hipLaunchKernelGGL(rp_pairs_kernel, dim3(sslam::cdiv(a.Q, 4)), dim3(256), 0, s, a);
+    const dim3 grid(sslam::cdiv(a.Q, 4)), block(256);
+    if (a.B == 0) {
+        hipLaunchKernelGGL(rp_pairs_kernel, grid, block, 0, s, a);
+    } else {                     // the widest load every frame row allows (rp_row_chunk)
+        const uintptr_t p = reinterpret_cast<uintptr_t>(a.des_u8);
+        if (a.B % 16 == 0 && p % 16 == 0) hipLaunchKernelGGL(rp_pairs_hamming_kernel<16>, grid, block, 0, s, a);
+        else if (a.B % 4 == 0 && p % 4 == 0) hipLaunchKernelGGL(rp_pairs_hamming_kernel<4>, grid, block, 0, s, a);
+        else hipLaunchKernelGGL(rp_pairs_hamming_kernel<1>, grid, block, 0, s, a);
+    }
     hipLaunchKernelGGL(rp_assign_kernel, dim3(1), dim3(64), (((size_t)a.N + 31) / 32) * 4, s, a);
     SSLAM_HIP_CHECK(hipGetLastError());
     return 0;
@@ -205,6 +304,69 @@ extern "C" int sslam_reproject_match_host(sslam_ctx* ctx, int n_points, const do
     SSLAM_HIP_CHECK(sslam::copy_down(s, info, a.info, 4));
     SSLAM_HIP_CHECK(hipStreamSynchronize(s));
     SSLAM_REQUIRE(info[1] == 0, "sslam_reproject_match_host: more than %d keypoints within %.1f px of one projection",
+                  RP_MAXC, radius_px);
+    if (info_out) { info_out[0] = info[0]; info_out[1] = info[2]; }
+    return 0;
+}
+
+/* The Hamming form of the device-resident variant: obs_desc_u8[n_points][6][64] (zero beyond desc_bytes, 16-byte aligned)
+ * and des_u8[n_kp][desc_bytes] (what sslam_orb_detect_dev writes) are device pointers.  n_kp_dev (may be NULL): the device
+ * count that the detector left, clamped to n_kp rows and read by the kernels - no synchronisation.  Enqueue only. */
+extern "C" int sslam_reproject_match_hamming_dev(sslam_ctx* ctx, int n_points, const double* pts3d, const int32_t* obs_cnt,
+                                                 const uint8_t* obs_desc_u8, const double* K9, const double* Tcw16, int n_kp,
+                                                 const float* kp_xy, const uint8_t* des_u8, int desc_bytes, int img_w,
+                                                 int img_h, double radius_px, double max_hamm, int32_t* kp_of_point,
+                                                 float* uv_out, int32_t* info_out, const int32_t* n_kp_dev) {
+    SSLAM_REQUIRE(ctx != nullptr, "sslam_reproject_match_hamming_dev: ctx is NULL");
+    SSLAM_REQUIRE(n_points > 0 && n_kp > 0, "sslam_reproject_match_hamming_dev: empty input (the caller returns early)");
+    SSLAM_REQUIRE(pts3d && obs_cnt && obs_desc_u8 && K9 && Tcw16 && kp_xy && des_u8 && kp_of_point && info_out,
+                  "sslam_reproject_match_hamming_dev: NULL argument");
+    SSLAM_REQUIRE(desc_bytes >= 2 && desc_bytes <= RP_HB, "sslam_reproject_match_hamming_dev: desc_bytes=%d not in [2,%d]",
+                  desc_bytes, RP_HB);
+    SSLAM_REQUIRE(reinterpret_cast<uintptr_t>(obs_desc_u8) % 16 == 0,
+                  "sslam_reproject_match_hamming_dev: obs_desc_u8 is not 16-byte aligned");
+    SSLAM_REQUIRE(radius_px >= 0.0 && img_w > 0 && img_h > 0, "sslam_reproject_match_hamming_dev: bad radius / image size");
+    SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
+    RMArgs a{};
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { rm_bind(sl, a, (size_t)n_points, (size_t)n_kp, false); })) return rc;
+    a.Q = n_points; a.N = n_kp; a.pts = pts3d; a.obs_cnt = obs_cnt; a.obs_u8 = obs_desc_u8; a.kp = kp_xy; a.des_u8 = des_u8;
+    a.B = desc_bytes; a.n_kp_dev = n_kp_dev;
+    if (uv_out) a.uv = uv_out;
+    a.kp_of_point = kp_of_point; a.info = info_out;
+    return rm_enqueue(ctx, a, K9, Tcw16, img_w, img_h, radius_px, max_hamm);
+}
+
+extern "C" int sslam_reproject_match_hamming_host(sslam_ctx* ctx, int n_points, const double* pts3d, const int32_t* obs_cnt,
+                                                  const uint8_t* obs_desc_u8, const double* K9, const double* Tcw16, int n_kp,
+                                                  const float* kp_xy, const uint8_t* des_u8, int desc_bytes, int img_w,
+                                                  int img_h, double radius_px, double max_hamm, int32_t* kp_of_point,
+                                                  float* uv_out, int32_t* info_out) {
+    SSLAM_REQUIRE(ctx != nullptr, "sslam_reproject_match_hamming_host: ctx is NULL");
+    SSLAM_REQUIRE(n_points > 0 && n_kp > 0, "sslam_reproject_match_hamming_host: empty input (the caller returns early)");
+    SSLAM_REQUIRE(pts3d && obs_cnt && obs_desc_u8 && K9 && Tcw16 && kp_xy && des_u8 && kp_of_point,
+                  "sslam_reproject_match_hamming_host: NULL argument");
+    SSLAM_REQUIRE(desc_bytes >= 2 && desc_bytes <= RP_HB, "sslam_reproject_match_hamming_host: desc_bytes=%d not in [2,%d]",
+                  desc_bytes, RP_HB);
+    SSLAM_REQUIRE(radius_px >= 0.0 && img_w > 0 && img_h > 0, "sslam_reproject_match_hamming_host: bad radius / image size");
+    for (int q = 0; q < n_points; ++q)
+        SSLAM_REQUIRE(obs_cnt[q] >= 0 && obs_cnt[q] <= 6, "sslam_reproject_match_hamming_host: obs_cnt[%d]=%d not in [0,6]", q,
+                      obs_cnt[q]);
+    SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
+    const size_t Q = (size_t)n_points, N = (size_t)n_kp, B = (size_t)desc_bytes;
+    RMArgs a{};
+    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { rm_bind(sl, a, Q, N, true, B); })) return rc;
+    a.Q = n_points; a.N = n_kp; a.B = desc_bytes;
+    hipStream_t s = ctx->stream;
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.pts, pts3d, Q * 3)); SSLAM_HIP_CHECK(sslam::copy_up(s, a.obs_cnt, obs_cnt, Q));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.obs_u8, obs_desc_u8, Q * 6 * RP_HB));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.kp, kp_xy, N * 2)); SSLAM_HIP_CHECK(sslam::copy_up(s, a.des_u8, des_u8, N * B));
+    if (int rc = rm_enqueue(ctx, a, K9, Tcw16, img_w, img_h, radius_px, max_hamm)) return rc;
+    int32_t info[4] = {0, 0, 0, 0};
+    SSLAM_HIP_CHECK(sslam::copy_down(s, kp_of_point, a.kp_of_point, Q));
+    if (uv_out) SSLAM_HIP_CHECK(sslam::copy_down(s, uv_out, a.uv, Q * 2));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, info, a.info, 4));
+    SSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    SSLAM_REQUIRE(info[1] == 0, "sslam_reproject_match_hamming_host: more than %d keypoints within %.1f px of one projection",
                   RP_MAXC, radius_px);
     if (info_out) { info_out[0] = info[0]; info_out[1] = info[2]; }
     return 0;

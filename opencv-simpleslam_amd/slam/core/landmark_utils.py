@@ -16,6 +16,9 @@ ARE the storage:
                                                                      observations (valid ones first;
                                                                      count 0 when the LAST has none:
                                                                      the reference's skip rule)
+    _bcnt [Q] int32, _bdesc [Q,6,64] uint8                           the same for binary descriptors (ORB,
+                                                                     AKAZE): the `binary_width`-byte uint8 rows
+                                                                     among the last six, zero padded to 64
 
 `points` is a dict subclass that tells the map about every DIRECT mutation - `points.pop(pid)`
 (triangulation_utils.py:105), `points[pid] = MapPoint(id=.., position=..)` (the reference's tests),
@@ -27,7 +30,8 @@ consumer compacts away; an assigned landmark is attached to a fresh row at once.
 ba_utils.py:269) and `mp.position = X` (what the duplicate merge does, :157) both write the array
 in place.  `add_observation` refreshes the point's descriptor rows.  `device_arrays(ctx)` returns
 device pointers of (positions, counts, descriptors), uploading positions / counts whole (a few
-tens of KB) and only the descriptor rows touched since the last call.
+tens of KB) and only the descriptor rows touched since the last call.  `device_arrays_binary(ctx)` does the
+same for the binary mirror, with a dirty range of its own.
 """
 from __future__ import annotations
 
@@ -37,6 +41,7 @@ import numpy as np
 
 DESC_DIM = 128
 MAX_OBS_CHECK = 6
+BIN_ROW = 64                                             # bytes of a stored binary row; descriptors of 2..64 bytes are mirrored
 
 
 def _canon_desc(desc):
@@ -191,6 +196,12 @@ class Map:
         self._desc = np.zeros((cap, MAX_OBS_CHECK, DESC_DIM), np.float32)
         self._dirty_lo, self._dirty_hi = 0, 0            # descriptor rows [lo, hi) changed since the last device sync
         self._dev = None                                 # (ctx, cap, pts_ptr, cnt_ptr, desc_ptr)
+        # the binary mirror: the uint8 descriptors of `binary_width` bytes, same rule, own device buffers and dirty range
+        self.binary_width: Optional[int] = None          # fixed by the first uint8 descriptor of 2..64 bytes that is stored
+        self._bcnt = np.zeros(cap, np.int32)
+        self._bdesc = np.zeros((cap, MAX_OBS_CHECK, BIN_ROW), np.uint8)
+        self._bdirty_lo, self._bdirty_hi = 0, 0
+        self._bdev = None
 
     @classmethod
     def from_reference(cls, ref_map) -> "Map":
@@ -231,7 +242,7 @@ class Map:
         if need <= cap:
             return
         new = max(need, 2 * cap)
-        for name in ("_ids", "_pos", "_col", "_dcnt", "_desc"):
+        for name in ("_ids", "_pos", "_col", "_dcnt", "_desc", "_bcnt", "_bdesc"):
             old = getattr(self, name)
             arr = np.zeros((new,) + old.shape[1:], old.dtype)
             arr[:cap] = old
@@ -239,10 +250,15 @@ class Map:
         self._col[cap:] = 1.0
 
     def _touch(self, lo: int, hi: int) -> None:
+        """Rows [lo, hi) changed: both device mirrors have to fetch them (each clears its own range)."""
         if self._dirty_lo == self._dirty_hi:
             self._dirty_lo, self._dirty_hi = lo, hi
         else:
             self._dirty_lo, self._dirty_hi = min(self._dirty_lo, lo), max(self._dirty_hi, hi)
+        if self._bdirty_lo == self._bdirty_hi:
+            self._bdirty_lo, self._bdirty_hi = lo, hi
+        else:
+            self._bdirty_lo, self._bdirty_hi = min(self._bdirty_lo, lo), max(self._bdirty_hi, hi)
 
     def add_points(self, pts3d: np.ndarray, colours: Optional[np.ndarray] = None, keyframe_idx: int = -1) -> List[int]:
         """Add a set of 3-D points and return the list of newly assigned ids (reference :99-117)."""
@@ -256,6 +272,7 @@ class Map:
         self._pos[r0:r0 + k] = pts3d.astype(np.float64)
         self._col[r0:r0 + k] = 1.0 if colours is None else np.asarray(colours, np.float32)
         self._dcnt[r0:r0 + k] = 0
+        self._bcnt[r0:r0 + k] = 0
         new_ids = list(range(self._next_pid, self._next_pid + k))
         self._ids[r0:r0 + k] = new_ids
         for j, pid in enumerate(new_ids):
@@ -306,7 +323,7 @@ class Map:
             return
         keep = np.fromiter((mp._row for mp in self.points.values()), np.int64, len(self.points))
         n = len(keep)
-        for name in ("_ids", "_pos", "_col", "_dcnt", "_desc"):
+        for name in ("_ids", "_pos", "_col", "_dcnt", "_desc", "_bcnt", "_bdesc"):
             arr = getattr(self, name)
             arr[:n] = arr[keep]                          # keep is increasing: fancy indexing copies first
         for r, mp in enumerate(self.points.values()):
@@ -318,20 +335,31 @@ class Map:
     def _refresh_desc(self, mp: MapPoint) -> None:
         """Descriptor rows of one landmark from its observation list (pnp_utils.py:46-50, :107-120,
         :270-272: last six observations, those with a 128-d float descriptor, none at all when the
-        LAST observation has no descriptor)."""
+        LAST observation has no descriptor).  The uint8 rows of `binary_width` bytes go to the binary
+        mirror by the same rule; a uint8 row of another width (the 1-byte placeholder that
+        triangulation_utils stores among them) is in neither: the reference scores it `inf`."""
         r = mp._row
         obs = mp.observations
-        n = 0
+        n = nb = 0
         if obs and obs[-1][2] is not None:
             for _, _, d in obs[-MAX_OBS_CHECK:]:
                 if d is None:
                     continue
                 d = np.asarray(d).reshape(-1)
-                if d.shape[0] != DESC_DIM or d.dtype == np.uint8:
+                if d.dtype == np.uint8:
+                    if self.binary_width is None and 2 <= d.shape[0] <= BIN_ROW:
+                        self.binary_width = int(d.shape[0])
+                    if d.shape[0] == self.binary_width:
+                        self._bdesc[r, nb, :d.shape[0]] = d
+                        self._bdesc[r, nb, d.shape[0]:] = 0
+                        nb += 1
+                    continue
+                if d.shape[0] != DESC_DIM:
                     continue
                 self._desc[r, n] = d
                 n += 1
         self._dcnt[r] = n
+        self._bcnt[r] = nb
         self._touch(r, r + 1)
 
     def resync(self) -> None:
@@ -361,6 +389,13 @@ class Map:
         self._compact()
         n = self._n
         return self._ids[:n], self._pos[:n], self._dcnt[:n], self._desc[:n]
+
+    def soa_binary(self):
+        """(ids [Q], positions [Q,3], binary descriptor counts [Q], rows [Q,6,64] uint8, zero beyond
+        `binary_width`) in dict order - views."""
+        self._compact()
+        n = self._n
+        return self._ids[:n], self._pos[:n], self._bcnt[:n], self._bdesc[:n]
 
     # ---------------- Merging landmarks ---------------- #
     def fuse_closeby_duplicate_landmarks(self, radius: float = 0.05) -> None:
@@ -411,3 +446,29 @@ class Map:
                 ctx.h2d(d_desc + lo * row_bytes, self._desc[lo:hi])
         self._dirty_lo = self._dirty_hi = 0
         return d_pos, d_cnt, d_desc
+
+    def device_arrays_binary(self, ctx):
+        """Device pointers (positions f64 [Q,3], counts i32 [Q], rows u8 [Q,6,64]) of the binary mirror, brought up to
+        date like `device_arrays`: positions and counts whole, the rows touched since the last call of THIS method (its
+        dirty range and its buffers are its own: a float upload in between neither clears nor reuses them)."""
+        self._compact()
+        n = self._n
+        cap = len(self._ids)
+        row_bytes = MAX_OBS_CHECK * BIN_ROW
+        if self._bdev is None or self._bdev[0] is not ctx or self._bdev[1] != cap:
+            if self._bdev is not None:
+                old = self._bdev
+                old[0].sync()
+                for p in old[2:]:
+                    old[0].free(p)
+            self._bdev = (ctx, cap, ctx.malloc(cap * 24), ctx.malloc(cap * 4), ctx.malloc(cap * row_bytes))
+            self._bdirty_lo, self._bdirty_hi = 0, n
+        _, _, d_pos, d_cnt, d_rows = self._bdev
+        if n:
+            ctx.h2d(d_pos, self._pos[:n])
+            ctx.h2d(d_cnt, self._bcnt[:n])
+            lo, hi = self._bdirty_lo, min(self._bdirty_hi, n)
+            if hi > lo:
+                ctx.h2d(d_rows + lo * row_bytes, self._bdesc[lo:hi])
+        self._bdirty_lo = self._bdirty_hi = 0
+        return d_pos, d_cnt, d_rows

@@ -22,6 +22,7 @@ from ... import pnp as _pnp
 
 DESC_DIM = 128
 MAX_OBS_CHECK = 6
+BIN_ROW = 64                 # bytes of a stored binary observation row; descriptors of 2..64 bytes are covered
 
 
 @dataclass
@@ -86,10 +87,97 @@ def snapshot_map_points(world_map):
     return ids, pts, cnt, desc
 
 
+def snapshot_map_points_binary(world_map, width: int):
+    """`snapshot_map_points` for binary descriptors: per point the uint8 rows of exactly `width` bytes among its last
+    six observations (valid ones first, zero padded to 64 bytes; count 0 when the LAST observation has none).  A uint8
+    row of another width - the 1-byte placeholder of triangulation_utils - is left out: the reference scores it `inf`."""
+    items = list(world_map.points.items())
+    Q = len(items)
+    ids = np.fromiter((k for k, _ in items), np.int64, Q)
+    pts = np.empty((Q, 3), np.float64)
+    cnt = np.zeros(Q, np.int32)
+    rows = np.zeros((Q, MAX_OBS_CHECK, BIN_ROW), np.uint8)
+    for q, (_, mp) in enumerate(items):
+        pts[q] = mp.position
+        obs = mp.observations
+        if not obs or obs[-1][2] is None:
+            continue
+        n = 0
+        for _, _, d in obs[-MAX_OBS_CHECK:]:
+            if d is None:
+                continue
+            d = np.asarray(d).reshape(-1)
+            if d.dtype != np.uint8 or d.shape[0] != width:
+                continue
+            rows[q, n, :width] = d
+            n += 1
+        cnt[q] = n
+    return ids, pts, cnt, rows
+
+
+def _float_map_refusal(world_map, width):
+    """A binary frame found no uint8 row of its width in a non-empty map: refuse when the map holds float descriptors
+    (the reference would return no match, every distance being `inf`); a map without any descriptor just has no match."""
+    for mp in world_map.points.values():
+        for _, _, d in mp.observations:
+            if d is not None and np.asarray(d).dtype != np.uint8:
+                raise NotImplementedError(
+                    f"binary frame descriptors ({width} bytes) against a float-descriptor map: the reference matches "
+                    "nothing there (every distance is inf); this backend refuses instead of returning an empty record")
+
+
+def _match_hamming(world_map, Kd, Td, pts2d, des, img_w, img_h, radius_px, max_hamm, ctx):
+    """The Hamming branch (pnp_utils.py:264-266, `_desc_distance` :78-112).  Equal minima: the lowest keypoint index wins."""
+    des = np.ascontiguousarray(des).reshape(len(pts2d), -1)
+    B = des.shape[1]
+    if B > BIN_ROW:
+        raise ValueError(f"reproject_and_match_2d3d: binary descriptors of {B} bytes; this backend covers 2..{BIN_ROW}")
+    if B < 2:
+        raise ValueError(f"reproject_and_match_2d3d: binary descriptors of {B} byte; this backend covers 2..{BIN_ROW}")
+    P = _native.ptr
+    N = len(pts2d)
+    if hasattr(world_map, "device_arrays_binary"):
+        if world_map.binary_width is None:
+            _float_map_refusal(world_map, B)
+            return None
+        if world_map.binary_width != B:
+            raise ValueError(f"reproject_and_match_2d3d: frame descriptors of {B} bytes against a map whose binary "
+                             f"descriptors have {world_map.binary_width} bytes")
+        ids, pts, cnt, _ = world_map.soa_binary()
+        Q = len(ids)
+        if not cnt.any():
+            _float_map_refusal(world_map, B)
+            return None
+        d_pos, d_cnt, d_rows = world_map.device_arrays_binary(ctx)
+        scr = _dev_scratch(ctx, Q, N)
+        ctx.h2d(scr["kp"], pts2d); ctx.h2d(scr["des"], des)
+        _native.check(_native.lib().sslam_reproject_match_hamming_dev(
+            ctx.handle, Q, P(d_pos), P(d_cnt), P(d_rows), P(Kd), P(Td), N, P(scr["kp"]), P(scr["des"]), B,
+            int(img_w), int(img_h), float(radius_px), float(max_hamm), P(scr["out"]), None, P(scr["info"]), None),
+            "sslam_reproject_match_hamming_dev")
+        out = np.empty(Q, np.int32); info4 = np.empty(4, np.int32)
+        ctx.d2h(out, scr["out"]); ctx.d2h(info4, scr["info"])
+        if info4[1]:
+            raise _native.NativeError(f"more than the candidate capacity of keypoints within {radius_px} px of one projection")
+    else:
+        ids, pts, cnt, rows = snapshot_map_points_binary(world_map, B)
+        if not cnt.any():
+            _float_map_refusal(world_map, B)
+            return None
+        out = np.full(len(ids), -1, np.int32)
+        info = (C.c_int32 * 2)()
+        _native.check(_native.lib().sslam_reproject_match_hamming_host(
+            ctx.handle, len(ids), P(pts), P(cnt), P(rows), P(Kd), P(Td), N, P(pts2d), P(des), B, int(img_w), int(img_h),
+            float(radius_px), float(max_hamm), P(out), None, info), "sslam_reproject_match_hamming_host")
+    return ids, pts, out
+
+
 def reproject_and_match_2d3d(world_map, K, Tcw_pred, kps_cur, des_cur, img_w, img_h, radius_px: float = 12.0,
                              max_hamm: int = 64, max_l2: float = 0.8, use_cosine: bool = False, ctx=None):
-    """Same signature and result as the reference (float descriptors).  `use_cosine` changes nothing
-    there either: the distance is always L2, only the threshold's name differs (pnp_utils.py:118)."""
+    """Same signature and result as the reference.  Float descriptors: `use_cosine` changes nothing there either, the
+    distance is always L2, only the threshold's name differs (pnp_utils.py:118).  uint8 descriptors of 2..64 bytes: the
+    Hamming branch with `max_hamm`; where accepted minima tie, the lowest keypoint index wins (the reference's order
+    is cKDTree's traversal order there).  A uint8 frame against a float-descriptor map raises NotImplementedError."""
     empty = Matches2D3D(np.zeros((0, 3), np.float32), np.zeros((0, 2), np.float32), [], [])
     if des_cur is None or len(des_cur) == 0 or not world_map.points:
         return empty
@@ -98,7 +186,18 @@ def reproject_and_match_2d3d(world_map, K, Tcw_pred, kps_cur, des_cur, img_w, im
         return empty
     des = np.asarray(des_cur)
     if des.dtype == np.uint8:
-        raise NotImplementedError("binary (ORB) descriptors: the Hamming branch is outside this backend's scope")
+        ctx = ctx or _native.default_context()
+        r = _match_hamming(world_map, np.ascontiguousarray(K, np.float64).reshape(9),
+                           np.ascontiguousarray(Tcw_pred, np.float64).reshape(16), pts2d, des, img_w, img_h, radius_px,
+                           max_hamm, ctx)
+        if r is None:
+            return empty
+        ids, pts, out = r
+        hit = np.flatnonzero(out >= 0)
+        if len(hit) == 0:
+            return empty
+        return Matches2D3D(pts[hit].astype(np.float32), pts2d[out[hit]].copy(), [int(i) for i in out[hit]],
+                           [int(i) for i in ids[hit]])
     des = np.ascontiguousarray(des, np.float32).reshape(len(pts2d), -1)
     if des.shape[1] != DESC_DIM:
         raise ValueError("reproject_and_match_2d3d expects 128-d descriptors")
