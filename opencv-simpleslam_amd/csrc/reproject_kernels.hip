@@ -19,6 +19,9 @@
 // addresses, popcount of the XOR, no cross-lane step.  The distance is stored as an exact float (<= 512), so the greedy
 // pass serves both forms.  Equal minima: the lowest keypoint index wins (ascending lists + the strict `<` below).
 // HBM-bound: Q x 6 x 64 B of observation rows read once plus the gathered frame rows (N x B bytes, cache resident).
+//
+// Host half, below the kernels: the four C entries (float / Hamming x `_host` / `_dev`) each name themselves, the shared
+// parameters (RMCall) and their descriptor form (RMForm) to ONE argument check and one of two bodies, rm_dev or rm_host.
 #include "common.hpp"
 
 namespace {
@@ -214,31 +217,61 @@ __global__ __launch_bounds__(64) void rp_assign_kernel(RMArgs a) {
     a.info[2] = cands;
 }
 
-}  // namespace
+// ---- host half: the parameters every entry shares, as passed, and the descriptor form of a call
+struct RMCall {
+    sslam_ctx* ctx; int n_points; const double* pts3d; const int32_t* obs_cnt; const double *K9, *Tcw16; int n_kp;
+    const float* kp_xy; int img_w, img_h; double radius_px, max_dist; int32_t* kp_of_point; float* uv_out; int32_t* info_out;
+};
+struct RMForm {
+    const void* obs;              // stored rows [n_points][6]: float[RP_DIM], or uint8[RP_HB] (zero beyond B bytes)
+    const void* des;              // frame rows [n_kp]: float[RP_DIM], or uint8[B]
+    bool hamming; int B;          // B: 0 for float descriptors, else the bytes of a row as given (rm_check refuses a bad width)
+    const int32_t* n_kp_dev;      // Hamming `_dev` only; may be NULL
+    size_t obs_row() const { return hamming ? RP_HB : RP_DIM * sizeof(float); }       // bytes
+    size_t des_row() const { return hamming ? (size_t)B : RP_DIM * sizeof(float); }
+    void point(RMArgs& a) const {                                   // the form's fields of RMArgs
+        if (hamming) { a.obs_u8 = static_cast<const uint8_t*>(obs); a.des_u8 = static_cast<const uint8_t*>(des); }
+        else { a.obs_desc = static_cast<const float*>(obs); a.des = static_cast<const float*>(des); }
+        a.B = B; a.n_kp_dev = n_kp_dev;
+    }
+};
 
-namespace {
+// The argument contract; `who` is the entry that was called.  `_dev` reports through the device info[4] alone, so it needs
+// info_out, and its kernels read the caller's rows in place, so they must be aligned; `_host` can read obs_cnt, and does.
+int rm_check(const char* who, const RMCall& c, const RMForm& f, bool dev) {
+    SSLAM_REQUIRE(c.ctx != nullptr, "%s: ctx is NULL", who);
+    SSLAM_REQUIRE(c.n_points > 0 && c.n_kp > 0, "%s: empty input (the caller returns early)", who);
+    SSLAM_REQUIRE(c.pts3d && c.obs_cnt && f.obs && c.K9 && c.Tcw16 && c.kp_xy && f.des && c.kp_of_point && (c.info_out || !dev),
+                  "%s: NULL argument", who);
+    SSLAM_REQUIRE(!f.hamming || (f.B >= 2 && f.B <= RP_HB), "%s: desc_bytes=%d not in [2,%d]", who, f.B, RP_HB);
+    SSLAM_REQUIRE(!f.hamming || !dev || reinterpret_cast<uintptr_t>(f.obs) % 16 == 0, "%s: obs_desc_u8 is not 16-byte aligned",
+                  who);
+    SSLAM_REQUIRE(c.radius_px >= 0.0 && c.img_w > 0 && c.img_h > 0, "%s: bad radius / image size", who);
+    for (int q = 0; !dev && q < c.n_points; ++q)
+        SSLAM_REQUIRE(c.obs_cnt[q] >= 0 && c.obs_cnt[q] <= 6, "%s: obs_cnt[%d]=%d not in [0,6]", who, q, c.obs_cnt[q]);
+    return 0;
+}
 
-// the slab-backed pointers of RMArgs, in slab order.  host_inputs: the map and keypoint arrays are the slab's too
-// B: 0 for float descriptors, the row width in bytes for the Hamming form
-void rm_bind(sslam::Slab& sl, RMArgs& a, size_t Q, size_t N, bool host_inputs, size_t B = 0) {
+// the slab-backed pointers of RMArgs, in slab order.  staged: the map and keypoint arrays are the slab's too, and the rows
+// of this form are moved there (its obs / des become the slab's pieces)
+void rm_bind(sslam::Slab& sl, RMArgs& a, size_t Q, size_t N, RMForm* staged) {
     a.K = sl.take<double>(9); a.Tcw = sl.take<double>(16); a.uv = sl.take<float>(Q * 2); a.cand_n = sl.take<int32_t>(Q);
     a.cand_kp = sl.take<int32_t>(Q * RP_MAXC); a.cand_d = sl.take<float>(Q * RP_MAXC);
     a.kp_of_point = sl.take<int32_t>(Q); a.info = sl.take<int32_t>(4);
-    if (!host_inputs) return;
+    if (!staged) return;
     a.pts = sl.take<double>(Q * 3); a.obs_cnt = sl.take<int32_t>(Q); a.kp = sl.take<float>(N * 2);
-    if (B) { a.obs_u8 = sl.take<uint8_t>(Q * 6 * RP_HB); a.des_u8 = sl.take<uint8_t>(N * B); }
-    else { a.obs_desc = sl.take<float>(Q * 6 * RP_DIM); a.des = sl.take<float>(N * RP_DIM); }
+    staged->obs = sl.take<uint8_t>(Q * 6 * staged->obs_row()); staged->des = sl.take<uint8_t>(N * staged->des_row());
+    staged->point(a);
 }
 
 // enqueue the two kernels on device-resident inputs (`a`: every pointer set); K9 / Tcw16 are host values
-int rm_enqueue(sslam_ctx* ctx, RMArgs a, const double* K9, const double* Tcw16, int img_w, int img_h, double radius_px,
-               double max_dist) {
-    hipStream_t s = ctx->stream;
+int rm_enqueue(RMArgs a, const RMCall& c) {
+    hipStream_t s = c.ctx->stream;
     (void)hipGetLastError();     // (a stale error of another library on this thread is not ours)
-    SSLAM_HIP_CHECK(sslam::copy_up(s, a.K, K9, 9));
-    SSLAM_HIP_CHECK(sslam::copy_up(s, a.Tcw, Tcw16, 16));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.K, c.K9, 9));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.Tcw, c.Tcw16, 16));
     SSLAM_HIP_CHECK(hipMemsetAsync(a.info, 0, 16, s));
-    a.img_w = img_w; a.img_h = img_h; a.radius2 = radius_px * radius_px; a.thr = max_dist;
+    a.img_w = c.img_w; a.img_h = c.img_h; a.radius2 = c.radius_px * c.radius_px; a.thr = c.max_dist;
     const dim3 grid(sslam::cdiv(a.Q, 4)), block(256);
     if (a.B == 0) {
         hipLaunchKernelGGL(rp_pairs_kernel, grid, block, 0, s, a);
@@ -253,6 +286,45 @@ int rm_enqueue(sslam_ctx* ctx, RMArgs a, const double* K9, const double* Tcw16, 
     return 0;
 }
 
+// device-resident body: the caller's device arrays as they are; enqueue only
+int rm_dev(const char* who, const RMCall& c, const RMForm& f) {
+    if (int rc = rm_check(who, c, f, true)) return rc;
+    SSLAM_HIP_CHECK(hipSetDevice(c.ctx->device));
+    const size_t Q = (size_t)c.n_points, N = (size_t)c.n_kp;
+    RMArgs a{};
+    if (int rc = sslam::ctx_bind(c.ctx, [&](sslam::Slab& sl) { rm_bind(sl, a, Q, N, nullptr); })) return rc;
+    a.Q = c.n_points; a.N = c.n_kp; a.pts = c.pts3d; a.obs_cnt = c.obs_cnt; a.kp = c.kp_xy; f.point(a);
+    if (c.uv_out) a.uv = c.uv_out;
+    a.kp_of_point = c.kp_of_point; a.info = c.info_out;
+    return rm_enqueue(a, c);
+}
+
+// host-staged body: every array through the slab, one synchronisation, info_out[2] = {matches, candidates}
+int rm_host(const char* who, const RMCall& c, const RMForm& f) {
+    if (int rc = rm_check(who, c, f, false)) return rc;
+    SSLAM_HIP_CHECK(hipSetDevice(c.ctx->device));
+    const size_t Q = (size_t)c.n_points, N = (size_t)c.n_kp;
+    RMArgs a{};
+    RMForm d = f;                // the same form, rows in the slab
+    if (int rc = sslam::ctx_bind(c.ctx, [&](sslam::Slab& sl) { rm_bind(sl, a, Q, N, &d); })) return rc;
+    a.Q = c.n_points; a.N = c.n_kp;
+    hipStream_t s = c.ctx->stream;
+    const auto rows = [](const void* p) { return static_cast<const uint8_t*>(p); };     // rows travel as bytes
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.pts, c.pts3d, Q * 3)); SSLAM_HIP_CHECK(sslam::copy_up(s, a.obs_cnt, c.obs_cnt, Q));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, rows(d.obs), rows(f.obs), Q * 6 * f.obs_row()));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, a.kp, c.kp_xy, N * 2));
+    SSLAM_HIP_CHECK(sslam::copy_up(s, rows(d.des), rows(f.des), N * f.des_row()));
+    if (int rc = rm_enqueue(a, c)) return rc;
+    int32_t info[4] = {0, 0, 0, 0};
+    SSLAM_HIP_CHECK(sslam::copy_down(s, c.kp_of_point, a.kp_of_point, Q));
+    if (c.uv_out) SSLAM_HIP_CHECK(sslam::copy_down(s, c.uv_out, a.uv, Q * 2));
+    SSLAM_HIP_CHECK(sslam::copy_down(s, info, a.info, 4));
+    SSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    SSLAM_REQUIRE(info[1] == 0, "%s: more than %d keypoints within %.1f px of one projection", who, RP_MAXC, c.radius_px);
+    if (c.info_out) { c.info_out[0] = info[0]; c.info_out[1] = info[2]; }
+    return 0;
+}
+
 }  // namespace
 
 /* Device-resident variant: the map arrays (an incrementally maintained SoA map keeps them on the GPU)
@@ -263,50 +335,16 @@ extern "C" int sslam_reproject_match_dev(sslam_ctx* ctx, int n_points, const dou
                                          const float* obs_desc, const double* K9, const double* Tcw16, int n_kp,
                                          const float* kp_xy, const float* des, int img_w, int img_h, double radius_px,
                                          double max_dist, int32_t* kp_of_point, float* uv_out, int32_t* info_out) {
-    SSLAM_REQUIRE(ctx != nullptr, "sslam_reproject_match_dev: ctx is NULL");
-    SSLAM_REQUIRE(n_points > 0 && n_kp > 0, "sslam_reproject_match_dev: empty input (the caller returns early)");
-    SSLAM_REQUIRE(pts3d && obs_cnt && obs_desc && K9 && Tcw16 && kp_xy && des && kp_of_point && info_out,
-                  "sslam_reproject_match_dev: NULL argument");
-    SSLAM_REQUIRE(radius_px >= 0.0 && img_w > 0 && img_h > 0, "sslam_reproject_match_dev: bad radius / image size");
-    SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
-    RMArgs a{};
-    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { rm_bind(sl, a, (size_t)n_points, (size_t)n_kp, false); })) return rc;
-    a.Q = n_points; a.N = n_kp; a.pts = pts3d; a.obs_cnt = obs_cnt; a.obs_desc = obs_desc; a.kp = kp_xy; a.des = des;
-    if (uv_out) a.uv = uv_out;
-    a.kp_of_point = kp_of_point; a.info = info_out;
-    return rm_enqueue(ctx, a, K9, Tcw16, img_w, img_h, radius_px, max_dist);
+    return rm_dev("sslam_reproject_match_dev", {ctx, n_points, pts3d, obs_cnt, K9, Tcw16, n_kp, kp_xy, img_w, img_h, radius_px,
+                                                max_dist, kp_of_point, uv_out, info_out}, {obs_desc, des, false, 0, nullptr});
 }
 
 extern "C" int sslam_reproject_match_host(sslam_ctx* ctx, int n_points, const double* pts3d, const int32_t* obs_cnt,
                                           const float* obs_desc, const double* K9, const double* Tcw16, int n_kp,
                                           const float* kp_xy, const float* des, int img_w, int img_h, double radius_px,
                                           double max_dist, int32_t* kp_of_point, float* uv_out, int32_t* info_out) {
-    SSLAM_REQUIRE(ctx != nullptr, "sslam_reproject_match_host: ctx is NULL");
-    SSLAM_REQUIRE(n_points > 0 && n_kp > 0, "sslam_reproject_match_host: empty input (the caller returns early)");
-    SSLAM_REQUIRE(pts3d && obs_cnt && obs_desc && K9 && Tcw16 && kp_xy && des && kp_of_point,
-                  "sslam_reproject_match_host: NULL argument");
-    SSLAM_REQUIRE(radius_px >= 0.0 && img_w > 0 && img_h > 0, "sslam_reproject_match_host: bad radius / image size");
-    for (int q = 0; q < n_points; ++q)
-        SSLAM_REQUIRE(obs_cnt[q] >= 0 && obs_cnt[q] <= 6, "sslam_reproject_match_host: obs_cnt[%d]=%d not in [0,6]", q, obs_cnt[q]);
-    SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t Q = (size_t)n_points, N = (size_t)n_kp;
-    RMArgs a{};
-    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { rm_bind(sl, a, Q, N, true); })) return rc;
-    a.Q = n_points; a.N = n_kp;
-    hipStream_t s = ctx->stream;
-    SSLAM_HIP_CHECK(sslam::copy_up(s, a.pts, pts3d, Q * 3)); SSLAM_HIP_CHECK(sslam::copy_up(s, a.obs_cnt, obs_cnt, Q));
-    SSLAM_HIP_CHECK(sslam::copy_up(s, a.obs_desc, obs_desc, Q * 6 * RP_DIM));
-    SSLAM_HIP_CHECK(sslam::copy_up(s, a.kp, kp_xy, N * 2)); SSLAM_HIP_CHECK(sslam::copy_up(s, a.des, des, N * RP_DIM));
-    if (int rc = rm_enqueue(ctx, a, K9, Tcw16, img_w, img_h, radius_px, max_dist)) return rc;
-    int32_t info[4] = {0, 0, 0, 0};
-    SSLAM_HIP_CHECK(sslam::copy_down(s, kp_of_point, a.kp_of_point, Q));
-    if (uv_out) SSLAM_HIP_CHECK(sslam::copy_down(s, uv_out, a.uv, Q * 2));
-    SSLAM_HIP_CHECK(sslam::copy_down(s, info, a.info, 4));
-    SSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    SSLAM_REQUIRE(info[1] == 0, "sslam_reproject_match_host: more than %d keypoints within %.1f px of one projection",
-                  RP_MAXC, radius_px);
-    if (info_out) { info_out[0] = info[0]; info_out[1] = info[2]; }
-    return 0;
+    return rm_host("sslam_reproject_match_host", {ctx, n_points, pts3d, obs_cnt, K9, Tcw16, n_kp, kp_xy, img_w, img_h, radius_px,
+                                                  max_dist, kp_of_point, uv_out, info_out}, {obs_desc, des, false, 0, nullptr});
 }
 
 /* The Hamming form of the device-resident variant: obs_desc_u8[n_points][6][64] (zero beyond desc_bytes, 16-byte aligned)
@@ -317,23 +355,9 @@ extern "C" int sslam_reproject_match_hamming_dev(sslam_ctx* ctx, int n_points, c
                                                  const float* kp_xy, const uint8_t* des_u8, int desc_bytes, int img_w,
                                                  int img_h, double radius_px, double max_hamm, int32_t* kp_of_point,
                                                  float* uv_out, int32_t* info_out, const int32_t* n_kp_dev) {
-    SSLAM_REQUIRE(ctx != nullptr, "sslam_reproject_match_hamming_dev: ctx is NULL");
-    SSLAM_REQUIRE(n_points > 0 && n_kp > 0, "sslam_reproject_match_hamming_dev: empty input (the caller returns early)");
-    SSLAM_REQUIRE(pts3d && obs_cnt && obs_desc_u8 && K9 && Tcw16 && kp_xy && des_u8 && kp_of_point && info_out,
-                  "sslam_reproject_match_hamming_dev: NULL argument");
-    SSLAM_REQUIRE(desc_bytes >= 2 && desc_bytes <= RP_HB, "sslam_reproject_match_hamming_dev: desc_bytes=%d not in [2,%d]",
-                  desc_bytes, RP_HB);
-    SSLAM_REQUIRE(reinterpret_cast<uintptr_t>(obs_desc_u8) % 16 == 0,
-                  "sslam_reproject_match_hamming_dev: obs_desc_u8 is not 16-byte aligned");
-    SSLAM_REQUIRE(radius_px >= 0.0 && img_w > 0 && img_h > 0, "sslam_reproject_match_hamming_dev: bad radius / image size");
-    SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
-    RMArgs a{};
-    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { rm_bind(sl, a, (size_t)n_points, (size_t)n_kp, false); })) return rc;
-    a.Q = n_points; a.N = n_kp; a.pts = pts3d; a.obs_cnt = obs_cnt; a.obs_u8 = obs_desc_u8; a.kp = kp_xy; a.des_u8 = des_u8;
-    a.B = desc_bytes; a.n_kp_dev = n_kp_dev;
-    if (uv_out) a.uv = uv_out;
-    a.kp_of_point = kp_of_point; a.info = info_out;
-    return rm_enqueue(ctx, a, K9, Tcw16, img_w, img_h, radius_px, max_hamm);
+    return rm_dev("sslam_reproject_match_hamming_dev", {ctx, n_points, pts3d, obs_cnt, K9, Tcw16, n_kp, kp_xy, img_w, img_h,
+                                                        radius_px, max_hamm, kp_of_point, uv_out, info_out},
+                  {obs_desc_u8, des_u8, true, desc_bytes, n_kp_dev});
 }
 
 extern "C" int sslam_reproject_match_hamming_host(sslam_ctx* ctx, int n_points, const double* pts3d, const int32_t* obs_cnt,
@@ -341,33 +365,7 @@ extern "C" int sslam_reproject_match_hamming_host(sslam_ctx* ctx, int n_points, 
                                                   const float* kp_xy, const uint8_t* des_u8, int desc_bytes, int img_w,
                                                   int img_h, double radius_px, double max_hamm, int32_t* kp_of_point,
                                                   float* uv_out, int32_t* info_out) {
-    SSLAM_REQUIRE(ctx != nullptr, "sslam_reproject_match_hamming_host: ctx is NULL");
-    SSLAM_REQUIRE(n_points > 0 && n_kp > 0, "sslam_reproject_match_hamming_host: empty input (the caller returns early)");
-    SSLAM_REQUIRE(pts3d && obs_cnt && obs_desc_u8 && K9 && Tcw16 && kp_xy && des_u8 && kp_of_point,
-                  "sslam_reproject_match_hamming_host: NULL argument");
-    SSLAM_REQUIRE(desc_bytes >= 2 && desc_bytes <= RP_HB, "sslam_reproject_match_hamming_host: desc_bytes=%d not in [2,%d]",
-                  desc_bytes, RP_HB);
-    SSLAM_REQUIRE(radius_px >= 0.0 && img_w > 0 && img_h > 0, "sslam_reproject_match_hamming_host: bad radius / image size");
-    for (int q = 0; q < n_points; ++q)
-        SSLAM_REQUIRE(obs_cnt[q] >= 0 && obs_cnt[q] <= 6, "sslam_reproject_match_hamming_host: obs_cnt[%d]=%d not in [0,6]", q,
-                      obs_cnt[q]);
-    SSLAM_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t Q = (size_t)n_points, N = (size_t)n_kp, B = (size_t)desc_bytes;
-    RMArgs a{};
-    if (int rc = sslam::ctx_bind(ctx, [&](sslam::Slab& sl) { rm_bind(sl, a, Q, N, true, B); })) return rc;
-    a.Q = n_points; a.N = n_kp; a.B = desc_bytes;
-    hipStream_t s = ctx->stream;
-    SSLAM_HIP_CHECK(sslam::copy_up(s, a.pts, pts3d, Q * 3)); SSLAM_HIP_CHECK(sslam::copy_up(s, a.obs_cnt, obs_cnt, Q));
-    SSLAM_HIP_CHECK(sslam::copy_up(s, a.obs_u8, obs_desc_u8, Q * 6 * RP_HB));
-    SSLAM_HIP_CHECK(sslam::copy_up(s, a.kp, kp_xy, N * 2)); SSLAM_HIP_CHECK(sslam::copy_up(s, a.des_u8, des_u8, N * B));
-    if (int rc = rm_enqueue(ctx, a, K9, Tcw16, img_w, img_h, radius_px, max_hamm)) return rc;
-    int32_t info[4] = {0, 0, 0, 0};
-    SSLAM_HIP_CHECK(sslam::copy_down(s, kp_of_point, a.kp_of_point, Q));
-    if (uv_out) SSLAM_HIP_CHECK(sslam::copy_down(s, uv_out, a.uv, Q * 2));
-    SSLAM_HIP_CHECK(sslam::copy_down(s, info, a.info, 4));
-    SSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    SSLAM_REQUIRE(info[1] == 0, "sslam_reproject_match_hamming_host: more than %d keypoints within %.1f px of one projection",
-                  RP_MAXC, radius_px);
-    if (info_out) { info_out[0] = info[0]; info_out[1] = info[2]; }
-    return 0;
+    return rm_host("sslam_reproject_match_hamming_host", {ctx, n_points, pts3d, obs_cnt, K9, Tcw16, n_kp, kp_xy, img_w, img_h,
+                                                          radius_px, max_hamm, kp_of_point, uv_out, info_out},
+                   {obs_desc_u8, des_u8, true, desc_bytes, nullptr});
 }

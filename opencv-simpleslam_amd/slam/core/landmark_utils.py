@@ -12,11 +12,11 @@ to rebuild the same arrays (9.7 ms of a 14 ms association call at 5000 points). 
 ARE the storage:
 
     _ids [Q] int64, _pos [Q,3] float64, _col [Q,3] float32          one row per landmark, dict order
-    _dcnt [Q] int32, _desc [Q,6,128] float32                         descriptors of the last six
+    _float.cnt [Q] int32, _float.rows [Q,6,128] float32              descriptors of the last six
                                                                      observations (valid ones first;
                                                                      count 0 when the LAST has none:
-                                                                     the reference's skip rule)
-    _bcnt [Q] int32, _bdesc [Q,6,64] uint8                           the same for binary descriptors (ORB,
+                                                                     the reference's rule, `gather_rows`)
+    _binary.cnt [Q] int32, _binary.rows [Q,6,64] uint8               the same for binary descriptors (ORB,
                                                                      AKAZE): the `binary_width`-byte uint8 rows
                                                                      among the last six, zero padded to 64
 
@@ -31,7 +31,7 @@ ba_utils.py:269) and `mp.position = X` (what the duplicate merge does, :157) bot
 in place.  `add_observation` refreshes the point's descriptor rows.  `device_arrays(ctx)` returns
 device pointers of (positions, counts, descriptors), uploading positions / counts whole (a few
 tens of KB) and only the descriptor rows touched since the last call.  `device_arrays_binary(ctx)` does the
-same for the binary mirror, with a dirty range of its own.
+same for the binary mirror: the two are one type, `_Mirror`, each with its own device buffers and dirty range.
 """
 from __future__ import annotations
 
@@ -56,6 +56,78 @@ def _canon_desc(desc):
     d = d.astype(np.float32, copy=False)
     n = np.linalg.norm(d) + 1e-8
     return (d / n).reshape(-1)
+
+
+def gather_rows(landmarks, pts, cnt, rows, width, uint8):
+    """THE walk from observation lists to descriptor rows (reference pnp_utils.py:46-50, :107-120, :270-272), for landmark
+    q of `landmarks`: rows[q, :cnt[q], :width] = the descriptors of `width` elements among its last six observations, in
+    order - none at all when it has no observation or the LAST one has no descriptor - and, unless `pts` is None,
+    pts[q] = its position.  uint8: True keeps uint8 descriptors only, False the others only, None any dtype (cast to
+    rows.dtype).  A width of None is fixed by the first kept descriptor of 2 .. rows.shape[2] elements.  -> the width."""
+    used = None if width is None else rows[:, :, :width]
+    for q, mp in enumerate(landmarks):
+        if pts is not None:
+            pts[q] = mp.position
+        obs = mp.observations
+        n = 0
+        if obs and obs[-1][2] is not None:
+            for _, _, d in obs[-MAX_OBS_CHECK:]:
+                if d is None:
+                    continue
+                d = np.asarray(d).reshape(-1)
+                if uint8 is not None and (d.dtype == np.uint8) != uint8:
+                    continue
+                if d.shape[0] != width:
+                    if width is not None or not 2 <= d.shape[0] <= rows.shape[2]:
+                        continue
+                    width = d.shape[0]
+                    used = rows[:, :, :width]
+                used[q, n] = d
+                n += 1
+        cnt[q] = n
+    return width
+
+
+def _grown(old: np.ndarray, new: int) -> np.ndarray:
+    return np.concatenate([old, np.zeros((new - len(old),) + old.shape[1:], old.dtype)])
+
+
+class _Mirror:
+    """One descriptor form of the map, host and device: per landmark a count and [6][width] rows (valid ones first, zero
+    beyond a narrower row), the range of rows changed since the last `sync`, and the device buffers - positions, counts and
+    rows of its own, so that neither form's upload clears or reuses the other's."""
+
+    def __init__(self, cap: int, width: int, dtype) -> None:
+        self.cnt = np.zeros(cap, np.int32)
+        self.rows = np.zeros((cap, MAX_OBS_CHECK, width), dtype)
+        self.lo = self.hi = 0                            # rows [lo, hi) changed since the last device sync
+        self.dev = None                                  # (ctx, cap, pos_ptr, cnt_ptr, rows_ptr)
+
+    def touch(self, lo: int, hi: int) -> None:
+        self.lo, self.hi = (lo, hi) if self.lo == self.hi else (min(self.lo, lo), max(self.hi, hi))
+
+    def sync(self, ctx, pos: np.ndarray, n: int):
+        """Device pointers (positions f64 [n,3], counts i32 [n], rows [n,6,width]) on `ctx`'s GPU, brought up to date:
+        positions and counts are uploaded whole (BA rewrites positions in place without telling anyone; 28 bytes per
+        landmark), rows only where touched since the last call.  Another context or capacity: new buffers, everything."""
+        cap = len(self.cnt)
+        row_bytes = self.rows[0].nbytes
+        if self.dev is None or self.dev[0] is not ctx or self.dev[1] != cap:
+            if self.dev is not None:
+                self.dev[0].sync()
+                for p in self.dev[2:]:
+                    self.dev[0].free(p)
+            self.dev = (ctx, cap, ctx.malloc(cap * 24), ctx.malloc(cap * 4), ctx.malloc(cap * row_bytes))
+            self.lo, self.hi = 0, n
+        _, _, d_pos, d_cnt, d_rows = self.dev
+        if n:
+            ctx.h2d(d_pos, pos[:n])
+            ctx.h2d(d_cnt, self.cnt[:n])
+            lo, hi = self.lo, min(self.hi, n)
+            if hi > lo:
+                ctx.h2d(d_rows + lo * row_bytes, self.rows[lo:hi])
+        self.lo = self.hi = 0
+        return d_pos, d_cnt, d_rows
 
 
 class MapPoint:
@@ -192,16 +264,11 @@ class Map:
         self._ids = np.zeros(cap, np.int64)
         self._pos = np.zeros((cap, 3), np.float64)
         self._col = np.ones((cap, 3), np.float32)
-        self._dcnt = np.zeros(cap, np.int32)
-        self._desc = np.zeros((cap, MAX_OBS_CHECK, DESC_DIM), np.float32)
-        self._dirty_lo, self._dirty_hi = 0, 0            # descriptor rows [lo, hi) changed since the last device sync
-        self._dev = None                                 # (ctx, cap, pts_ptr, cnt_ptr, desc_ptr)
+        self._float = _Mirror(cap, DESC_DIM, np.float32)
         # the binary mirror: the uint8 descriptors of `binary_width` bytes, same rule, own device buffers and dirty range
         self.binary_width: Optional[int] = None          # fixed by the first uint8 descriptor of 2..64 bytes that is stored
-        self._bcnt = np.zeros(cap, np.int32)
-        self._bdesc = np.zeros((cap, MAX_OBS_CHECK, BIN_ROW), np.uint8)
-        self._bdirty_lo, self._bdirty_hi = 0, 0
-        self._bdev = None
+        self._binary = _Mirror(cap, BIN_ROW, np.uint8)
+        self._mirrors = (self._float, self._binary)
 
     @classmethod
     def from_reference(cls, ref_map) -> "Map":
@@ -242,23 +309,15 @@ class Map:
         if need <= cap:
             return
         new = max(need, 2 * cap)
-        for name in ("_ids", "_pos", "_col", "_dcnt", "_desc", "_bcnt", "_bdesc"):
-            old = getattr(self, name)
-            arr = np.zeros((new,) + old.shape[1:], old.dtype)
-            arr[:cap] = old
-            setattr(self, name, arr)
+        self._ids, self._pos, self._col = _grown(self._ids, new), _grown(self._pos, new), _grown(self._col, new)
         self._col[cap:] = 1.0
+        for m in self._mirrors:
+            m.cnt, m.rows = _grown(m.cnt, new), _grown(m.rows, new)
 
     def _touch(self, lo: int, hi: int) -> None:
         """Rows [lo, hi) changed: both device mirrors have to fetch them (each clears its own range)."""
-        if self._dirty_lo == self._dirty_hi:
-            self._dirty_lo, self._dirty_hi = lo, hi
-        else:
-            self._dirty_lo, self._dirty_hi = min(self._dirty_lo, lo), max(self._dirty_hi, hi)
-        if self._bdirty_lo == self._bdirty_hi:
-            self._bdirty_lo, self._bdirty_hi = lo, hi
-        else:
-            self._bdirty_lo, self._bdirty_hi = min(self._bdirty_lo, lo), max(self._bdirty_hi, hi)
+        for m in self._mirrors:
+            m.touch(lo, hi)
 
     def add_points(self, pts3d: np.ndarray, colours: Optional[np.ndarray] = None, keyframe_idx: int = -1) -> List[int]:
         """Add a set of 3-D points and return the list of newly assigned ids (reference :99-117)."""
@@ -271,8 +330,8 @@ class Map:
         r0 = self._n
         self._pos[r0:r0 + k] = pts3d.astype(np.float64)
         self._col[r0:r0 + k] = 1.0 if colours is None else np.asarray(colours, np.float32)
-        self._dcnt[r0:r0 + k] = 0
-        self._bcnt[r0:r0 + k] = 0
+        for m in self._mirrors:
+            m.cnt[r0:r0 + k] = 0
         new_ids = list(range(self._next_pid, self._next_pid + k))
         self._ids[r0:r0 + k] = new_ids
         for j, pid in enumerate(new_ids):
@@ -323,8 +382,7 @@ class Map:
             return
         keep = np.fromiter((mp._row for mp in self.points.values()), np.int64, len(self.points))
         n = len(keep)
-        for name in ("_ids", "_pos", "_col", "_dcnt", "_desc", "_bcnt", "_bdesc"):
-            arr = getattr(self, name)
+        for arr in (self._ids, self._pos, self._col, *(a for m in self._mirrors for a in (m.cnt, m.rows))):
             arr[:n] = arr[keep]                          # keep is increasing: fancy indexing copies first
         for r, mp in enumerate(self.points.values()):
             mp._row = r
@@ -333,33 +391,13 @@ class Map:
         self._touch(0, n)
 
     def _refresh_desc(self, mp: MapPoint) -> None:
-        """Descriptor rows of one landmark from its observation list (pnp_utils.py:46-50, :107-120,
-        :270-272: last six observations, those with a 128-d float descriptor, none at all when the
-        LAST observation has no descriptor).  The uint8 rows of `binary_width` bytes go to the binary
-        mirror by the same rule; a uint8 row of another width (the 1-byte placeholder that
-        triangulation_utils stores among them) is in neither: the reference scores it `inf`."""
-        r = mp._row
-        obs = mp.observations
-        n = nb = 0
-        if obs and obs[-1][2] is not None:
-            for _, _, d in obs[-MAX_OBS_CHECK:]:
-                if d is None:
-                    continue
-                d = np.asarray(d).reshape(-1)
-                if d.dtype == np.uint8:
-                    if self.binary_width is None and 2 <= d.shape[0] <= BIN_ROW:
-                        self.binary_width = int(d.shape[0])
-                    if d.shape[0] == self.binary_width:
-                        self._bdesc[r, nb, :d.shape[0]] = d
-                        self._bdesc[r, nb, d.shape[0]:] = 0
-                        nb += 1
-                    continue
-                if d.shape[0] != DESC_DIM:
-                    continue
-                self._desc[r, n] = d
-                n += 1
-        self._dcnt[r] = n
-        self._bcnt[r] = nb
+        """Descriptor rows of one landmark from its observation list (`gather_rows`): the 128-d descriptors that are not
+        uint8 go to the float mirror, the uint8 rows of `binary_width` bytes - fixed by the first of 2..64 bytes - to the
+        binary one (their bytes beyond the width are never written: zero).  A uint8 row of another width (the 1-byte
+        placeholder that triangulation_utils stores among them) is in neither: the reference scores it `inf`."""
+        r, f, b = mp._row, self._float, self._binary
+        gather_rows((mp,), None, f.cnt[r:], f.rows[r:], DESC_DIM, False)
+        self.binary_width = gather_rows((mp,), None, b.cnt[r:], b.rows[r:], self.binary_width, True)
         self._touch(r, r + 1)
 
     def resync(self) -> None:
@@ -388,14 +426,14 @@ class Map:
         """(ids [Q], positions [Q,3], descriptor counts [Q], descriptors [Q,6,128]) in dict order - views."""
         self._compact()
         n = self._n
-        return self._ids[:n], self._pos[:n], self._dcnt[:n], self._desc[:n]
+        return self._ids[:n], self._pos[:n], self._float.cnt[:n], self._float.rows[:n]
 
     def soa_binary(self):
         """(ids [Q], positions [Q,3], binary descriptor counts [Q], rows [Q,6,64] uint8, zero beyond
         `binary_width`) in dict order - views."""
         self._compact()
         n = self._n
-        return self._ids[:n], self._pos[:n], self._bcnt[:n], self._bdesc[:n]
+        return self._ids[:n], self._pos[:n], self._binary.cnt[:n], self._binary.rows[:n]
 
     # ---------------- Merging landmarks ---------------- #
     def fuse_closeby_duplicate_landmarks(self, radius: float = 0.05) -> None:
@@ -421,54 +459,13 @@ class Map:
 
     # ---------------- device mirror --------------------- #
     def device_arrays(self, ctx):
-        """Device pointers (positions f64 [Q,3], counts i32 [Q], descriptors f32 [Q,6,128]) of the current
-        map on `ctx`'s GPU, brought up to date: positions and counts are uploaded whole (BA rewrites
-        positions in place without telling anyone; 28 bytes per landmark), descriptors only for the
-        rows touched since the last call."""
+        """Device pointers (positions f64 [Q,3], counts i32 [Q], descriptors f32 [Q,6,128]) of the current map on `ctx`'s
+        GPU, brought up to date (`_Mirror.sync`)."""
         self._compact()
-        n = self._n
-        cap = len(self._ids)
-        row_bytes = MAX_OBS_CHECK * DESC_DIM * 4
-        if self._dev is None or self._dev[0] is not ctx or self._dev[1] != cap:
-            if self._dev is not None:
-                old = self._dev
-                old[0].sync()
-                for p in old[2:]:
-                    old[0].free(p)
-            self._dev = (ctx, cap, ctx.malloc(cap * 24), ctx.malloc(cap * 4), ctx.malloc(cap * row_bytes))
-            self._dirty_lo, self._dirty_hi = 0, n
-        _, _, d_pos, d_cnt, d_desc = self._dev
-        if n:
-            ctx.h2d(d_pos, self._pos[:n])
-            ctx.h2d(d_cnt, self._dcnt[:n])
-            lo, hi = self._dirty_lo, min(self._dirty_hi, n)
-            if hi > lo:
-                ctx.h2d(d_desc + lo * row_bytes, self._desc[lo:hi])
-        self._dirty_lo = self._dirty_hi = 0
-        return d_pos, d_cnt, d_desc
+        return self._float.sync(ctx, self._pos, self._n)
 
     def device_arrays_binary(self, ctx):
-        """Device pointers (positions f64 [Q,3], counts i32 [Q], rows u8 [Q,6,64]) of the binary mirror, brought up to
-        date like `device_arrays`: positions and counts whole, the rows touched since the last call of THIS method (its
-        dirty range and its buffers are its own: a float upload in between neither clears nor reuses them)."""
+        """Device pointers (positions f64 [Q,3], counts i32 [Q], rows u8 [Q,6,64]) of the binary mirror, brought up to date
+        the same way: the rows touched since the last call of THIS method (a float upload in between clears nothing)."""
         self._compact()
-        n = self._n
-        cap = len(self._ids)
-        row_bytes = MAX_OBS_CHECK * BIN_ROW
-        if self._bdev is None or self._bdev[0] is not ctx or self._bdev[1] != cap:
-            if self._bdev is not None:
-                old = self._bdev
-                old[0].sync()
-                for p in old[2:]:
-                    old[0].free(p)
-            self._bdev = (ctx, cap, ctx.malloc(cap * 24), ctx.malloc(cap * 4), ctx.malloc(cap * row_bytes))
-            self._bdirty_lo, self._bdirty_hi = 0, n
-        _, _, d_pos, d_cnt, d_rows = self._bdev
-        if n:
-            ctx.h2d(d_pos, self._pos[:n])
-            ctx.h2d(d_cnt, self._bcnt[:n])
-            lo, hi = self._bdirty_lo, min(self._bdirty_hi, n)
-            if hi > lo:
-                ctx.h2d(d_rows + lo * row_bytes, self._bdesc[lo:hi])
-        self._bdirty_lo = self._bdirty_hi = 0
-        return d_pos, d_cnt, d_rows
+        return self._binary.sync(ctx, self._pos, self._n)

@@ -19,10 +19,7 @@ import numpy as np
 
 from ... import _native
 from ... import pnp as _pnp
-
-DESC_DIM = 128
-MAX_OBS_CHECK = 6
-BIN_ROW = 64                 # bytes of a stored binary observation row; descriptors of 2..64 bytes are covered
+from .landmark_utils import BIN_ROW, DESC_DIM, MAX_OBS_CHECK, gather_rows
 
 
 @dataclass
@@ -59,60 +56,28 @@ def _kp_coords(kps):
     return np.ascontiguousarray(kps[:, :2], np.float32)
 
 
-def snapshot_map_points(world_map):
-    """SoA view of `world_map.points` for the kernel: ids, positions, and per point the descriptors
-    of its last six observations (valid ones first; count 0 when the LAST observation has none,
-    which is the reference's skip rule, pnp_utils.py:46-50 / :270-272)."""
-    items = list(world_map.points.items())
-    Q = len(items)
-    ids = np.fromiter((k for k, _ in items), np.int64, Q)
+def _snapshot(world_map, dtype, stored, width, uint8):
+    """SoA view of `world_map.points` for the kernel: ids, positions, and per point the count and the rows of `width`
+    elements that `gather_rows` - the reference's skip rule - keeps, in zeroed rows of `stored` elements."""
+    Q = len(world_map.points)
+    ids = np.fromiter(world_map.points.keys(), np.int64, Q)
     pts = np.empty((Q, 3), np.float64)
     cnt = np.zeros(Q, np.int32)
-    desc = np.zeros((Q, MAX_OBS_CHECK, DESC_DIM), np.float32)
-    for q, (_, mp) in enumerate(items):
-        pts[q] = mp.position
-        obs = mp.observations
-        if not obs or obs[-1][2] is None:
-            continue
-        n = 0
-        for _, _, d in obs[-MAX_OBS_CHECK:]:
-            if d is None:
-                continue
-            d = np.asarray(d).reshape(-1)
-            if d.shape[0] != DESC_DIM:
-                continue
-            desc[q, n] = d
-            n += 1
-        cnt[q] = n
-    return ids, pts, cnt, desc
+    rows = np.zeros((Q, MAX_OBS_CHECK, stored), dtype)
+    gather_rows(world_map.points.values(), pts, cnt, rows, width, uint8)
+    return ids, pts, cnt, rows
+
+
+def snapshot_map_points(world_map):
+    """The float form: the 128-d descriptors (whatever their dtype, cast to float32) among the last six observations,
+    valid ones first; count 0 when the LAST observation has none (pnp_utils.py:46-50 / :270-272)."""
+    return _snapshot(world_map, np.float32, DESC_DIM, DESC_DIM, None)
 
 
 def snapshot_map_points_binary(world_map, width: int):
-    """`snapshot_map_points` for binary descriptors: per point the uint8 rows of exactly `width` bytes among its last
-    six observations (valid ones first, zero padded to 64 bytes; count 0 when the LAST observation has none).  A uint8
-    row of another width - the 1-byte placeholder of triangulation_utils - is left out: the reference scores it `inf`."""
-    items = list(world_map.points.items())
-    Q = len(items)
-    ids = np.fromiter((k for k, _ in items), np.int64, Q)
-    pts = np.empty((Q, 3), np.float64)
-    cnt = np.zeros(Q, np.int32)
-    rows = np.zeros((Q, MAX_OBS_CHECK, BIN_ROW), np.uint8)
-    for q, (_, mp) in enumerate(items):
-        pts[q] = mp.position
-        obs = mp.observations
-        if not obs or obs[-1][2] is None:
-            continue
-        n = 0
-        for _, _, d in obs[-MAX_OBS_CHECK:]:
-            if d is None:
-                continue
-            d = np.asarray(d).reshape(-1)
-            if d.dtype != np.uint8 or d.shape[0] != width:
-                continue
-            rows[q, n, :width] = d
-            n += 1
-        cnt[q] = n
-    return ids, pts, cnt, rows
+    """The binary form: the uint8 rows of exactly `width` bytes, zero padded to 64.  A uint8 row of another width - the
+    1-byte placeholder of triangulation_utils - is left out: the reference scores it `inf`."""
+    return _snapshot(world_map, np.uint8, BIN_ROW, width, True)
 
 
 def _float_map_refusal(world_map, width):
@@ -126,49 +91,61 @@ def _float_map_refusal(world_map, width):
                     "nothing there (every distance is inf); this backend refuses instead of returning an empty record")
 
 
-def _match_hamming(world_map, Kd, Td, pts2d, des, img_w, img_h, radius_px, max_hamm, ctx):
-    """The Hamming branch (pnp_utils.py:264-266, `_desc_distance` :78-112).  Equal minima: the lowest keypoint index wins."""
-    des = np.ascontiguousarray(des).reshape(len(pts2d), -1)
-    B = des.shape[1]
-    if B > BIN_ROW:
-        raise ValueError(f"reproject_and_match_2d3d: binary descriptors of {B} bytes; this backend covers 2..{BIN_ROW}")
-    if B < 2:
-        raise ValueError(f"reproject_and_match_2d3d: binary descriptors of {B} byte; this backend covers 2..{BIN_ROW}")
-    P = _native.ptr
-    N = len(pts2d)
-    if hasattr(world_map, "device_arrays_binary"):
+@dataclass(frozen=True)
+class _Form:
+    """One descriptor form of the association: what differs between the float and the Hamming branch."""
+    dtype: type                # of a descriptor element
+    stored: int                # elements of a stored observation row
+    binary: bool               # the native entries take the row width, and a map may hold no row of the frame's form
+    dev: str                   # native entry on the SoA map's device arrays
+    host: str                  # native entry on host arrays
+    soa: str                   # the SoA map's host accessor ...
+    device_arrays: str         # ... and its device accessor (a map that has it IS an SoA map)
+
+
+_FLOAT = _Form(np.float32, DESC_DIM, False, "sslam_reproject_match_dev", "sslam_reproject_match_host", "soa", "device_arrays")
+_HAMMING = _Form(np.uint8, BIN_ROW, True, "sslam_reproject_match_hamming_dev", "sslam_reproject_match_hamming_host",
+                 "soa_binary", "device_arrays_binary")
+
+
+def _associate(f, world_map, K, Tcw_pred, pts2d, des, img_w, img_h, radius_px, thr, ctx):
+    """kp_of_point per map point for frame rows `des` [N][B] of form `f` -> (ids, positions, kp_of_point), or None where a
+    binary frame finds no row of its form in the map.  Hamming (pnp_utils.py:264-266, `_desc_distance` :78-112): equal
+    minima go to the lowest keypoint index."""
+    P, lib, (N, B) = _native.ptr, _native.lib(), des.shape
+    Kd, Td = np.ascontiguousarray(K, np.float64).reshape(9), np.ascontiguousarray(Tcw_pred, np.float64).reshape(16)
+    soa = hasattr(world_map, f.device_arrays)
+    if f.binary and soa and world_map.binary_width != B:
         if world_map.binary_width is None:
             _float_map_refusal(world_map, B)
             return None
-        if world_map.binary_width != B:
-            raise ValueError(f"reproject_and_match_2d3d: frame descriptors of {B} bytes against a map whose binary "
-                             f"descriptors have {world_map.binary_width} bytes")
-        ids, pts, cnt, _ = world_map.soa_binary()
-        Q = len(ids)
-        if not cnt.any():
-            _float_map_refusal(world_map, B)
-            return None
-        d_pos, d_cnt, d_rows = world_map.device_arrays_binary(ctx)
+        raise ValueError(f"reproject_and_match_2d3d: frame descriptors of {B} bytes against a map whose binary "
+                         f"descriptors have {world_map.binary_width} bytes")
+    ids, pts, cnt, rows = getattr(world_map, f.soa)() if soa else _snapshot(world_map, f.dtype, f.stored, B, f.binary or None)
+    if f.binary and not cnt.any():
+        _float_map_refusal(world_map, B)
+        return None
+    Q = len(ids)
+
+    def call(entry, m_pos, m_cnt, m_rows, kp, frame, out, info, *n_kp_dev):
+        _native.check(getattr(lib, entry)(
+            ctx.handle, Q, P(m_pos), P(m_cnt), P(m_rows), P(Kd), P(Td), N, P(kp), P(frame), *((B,) if f.binary else ()),
+            int(img_w), int(img_h), float(radius_px), float(thr), P(out), None, info, *n_kp_dev), entry)
+    if soa:
+        # SoA map (slam/core/landmark_utils.py of this overlay): its arrays already live on the GPU,
+        # only the rows touched since the last call travel; no walk over the dict of objects
+        d_map = getattr(world_map, f.device_arrays)(ctx)
         scr = _dev_scratch(ctx, Q, N)
         ctx.h2d(scr["kp"], pts2d); ctx.h2d(scr["des"], des)
-        _native.check(_native.lib().sslam_reproject_match_hamming_dev(
-            ctx.handle, Q, P(d_pos), P(d_cnt), P(d_rows), P(Kd), P(Td), N, P(scr["kp"]), P(scr["des"]), B,
-            int(img_w), int(img_h), float(radius_px), float(max_hamm), P(scr["out"]), None, P(scr["info"]), None),
-            "sslam_reproject_match_hamming_dev")
+        call(f.dev, *d_map, scr["kp"], scr["des"], scr["out"], P(scr["info"]),
+             *((None,) if f.binary else ()))     # (n_kp_dev: every frame row uploaded here is live)
         out = np.empty(Q, np.int32); info4 = np.empty(4, np.int32)
         ctx.d2h(out, scr["out"]); ctx.d2h(info4, scr["info"])
         if info4[1]:
             raise _native.NativeError(f"more than the candidate capacity of keypoints within {radius_px} px of one projection")
     else:
-        ids, pts, cnt, rows = snapshot_map_points_binary(world_map, B)
-        if not cnt.any():
-            _float_map_refusal(world_map, B)
-            return None
-        out = np.full(len(ids), -1, np.int32)
-        info = (C.c_int32 * 2)()
-        _native.check(_native.lib().sslam_reproject_match_hamming_host(
-            ctx.handle, len(ids), P(pts), P(cnt), P(rows), P(Kd), P(Td), N, P(pts2d), P(des), B, int(img_w), int(img_h),
-            float(radius_px), float(max_hamm), P(out), None, info), "sslam_reproject_match_hamming_host")
+        out = np.full(Q, -1, np.int32)
+        call(f.host, pts, cnt, rows, pts2d, des, out, (C.c_int32 * 2)())
     return ids, pts, out
 
 
@@ -186,48 +163,22 @@ def reproject_and_match_2d3d(world_map, K, Tcw_pred, kps_cur, des_cur, img_w, im
         return empty
     des = np.asarray(des_cur)
     if des.dtype == np.uint8:
-        ctx = ctx or _native.default_context()
-        r = _match_hamming(world_map, np.ascontiguousarray(K, np.float64).reshape(9),
-                           np.ascontiguousarray(Tcw_pred, np.float64).reshape(16), pts2d, des, img_w, img_h, radius_px,
-                           max_hamm, ctx)
-        if r is None:
-            return empty
-        ids, pts, out = r
-        hit = np.flatnonzero(out >= 0)
-        if len(hit) == 0:
-            return empty
-        return Matches2D3D(pts[hit].astype(np.float32), pts2d[out[hit]].copy(), [int(i) for i in out[hit]],
-                           [int(i) for i in ids[hit]])
-    des = np.ascontiguousarray(des, np.float32).reshape(len(pts2d), -1)
-    if des.shape[1] != DESC_DIM:
-        raise ValueError("reproject_and_match_2d3d expects 128-d descriptors")
-    ctx = ctx or _native.default_context()
-    Kd = np.ascontiguousarray(K, np.float64).reshape(9)
-    Td = np.ascontiguousarray(Tcw_pred, np.float64).reshape(16)
-    P = _native.ptr
-    if hasattr(world_map, "device_arrays"):
-        # SoA map (slam/core/landmark_utils.py of this overlay): its arrays already live on the GPU,
-        # only the rows touched since the last call travel; no walk over the dict of objects
-        ids, pts, _, _ = world_map.soa()
-        Q = len(ids)
-        d_pos, d_cnt, d_desc = world_map.device_arrays(ctx)
-        scr = _dev_scratch(ctx, Q, len(pts2d))
-        ctx.h2d(scr["kp"], pts2d); ctx.h2d(scr["des"], des)
-        _native.check(_native.lib().sslam_reproject_match_dev(
-            ctx.handle, Q, P(d_pos), P(d_cnt), P(d_desc), P(Kd), P(Td), len(pts2d), P(scr["kp"]), P(scr["des"]),
-            int(img_w), int(img_h), float(radius_px), float(max_l2), P(scr["out"]), None, P(scr["info"])),
-            "sslam_reproject_match_dev")
-        out = np.empty(Q, np.int32); info4 = np.empty(4, np.int32)
-        ctx.d2h(out, scr["out"]); ctx.d2h(info4, scr["info"])
-        if info4[1]:
-            raise _native.NativeError(f"more than the candidate capacity of keypoints within {radius_px} px of one projection")
+        f, thr = _HAMMING, max_hamm
+        des = np.ascontiguousarray(des).reshape(len(pts2d), -1)
+        B = des.shape[1]
+        if B > BIN_ROW:
+            raise ValueError(f"reproject_and_match_2d3d: binary descriptors of {B} bytes; this backend covers 2..{BIN_ROW}")
+        if B < 2:
+            raise ValueError(f"reproject_and_match_2d3d: binary descriptors of {B} byte; this backend covers 2..{BIN_ROW}")
     else:
-        ids, pts, cnt, desc = snapshot_map_points(world_map)
-        out = np.full(len(ids), -1, np.int32)
-        info = (C.c_int32 * 2)()
-        _native.check(_native.lib().sslam_reproject_match_host(
-            ctx.handle, len(ids), P(pts), P(cnt), P(desc), P(Kd), P(Td), len(pts2d), P(pts2d), P(des), int(img_w), int(img_h),
-            float(radius_px), float(max_l2), P(out), None, info), "sslam_reproject_match_host")
+        f, thr = _FLOAT, max_l2
+        des = np.ascontiguousarray(des, np.float32).reshape(len(pts2d), -1)
+        if des.shape[1] != DESC_DIM:
+            raise ValueError("reproject_and_match_2d3d expects 128-d descriptors")
+    r = _associate(f, world_map, K, Tcw_pred, pts2d, des, img_w, img_h, radius_px, thr, ctx or _native.default_context())
+    if r is None:
+        return empty
+    ids, pts, out = r
     hit = np.flatnonzero(out >= 0)
     if len(hit) == 0:
         return empty

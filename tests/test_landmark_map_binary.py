@@ -1,4 +1,4 @@
-"""The binary mirror of the overlay's SoA map (slam/core/landmark_utils.py: `_bcnt`, `_bdesc`, `binary_width`,
+"""The binary mirror of the overlay's SoA map (slam/core/landmark_utils.py: `_binary`, `binary_width`,
 `soa_binary`, `device_arrays_binary`): after every kind of mutation it equals what a walk over the dict of objects
 rebuilds (pnp_utils.snapshot_map_points_binary), it follows the reference's skip rule, it travels to the device by
 touched rows with a dirty range of its own, and a float-only map is what it was before the mirror existed.  The device
@@ -100,7 +100,7 @@ def test_mirror_follows_every_mutation(L, P):
     # growth past the initial capacity keeps the rows
     keep = m.soa_binary()[3][:5].copy()
     big = m.add_points(rng.uniform(-1, 1, (3000, 3)))
-    assert len(m._bcnt) >= len(m) > 1024 and len(m._bdesc) == len(m._bcnt)
+    assert len(m._binary.cnt) >= len(m) > 1024 and len(m._binary.rows) == len(m._binary.cnt)
     m.points[big[-1]].add_observation(9, 9, rows(rng))
     _, _, cnt, brows = check(m, P)
     np.testing.assert_array_equal(brows[:5], keep)
