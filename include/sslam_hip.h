@@ -572,6 +572,67 @@ int sslam_sift_octave_info(sslam_sift* o, int octave, int* info8);
 int sslam_sift_stage_read(sslam_sift* o, int octave, float* gauss, float* dog, int32_t* cand, int32_t* ref, float* hist,
                           int32_t* counts);
 
+/* --------------------------------------------------------------------- AKAZE
+ * Replaces `cv2.AKAZE_create(descriptor_type, descriptor_size, descriptor_channels, threshold, nOctaves, nOctaveLayers,
+ * diffusivity, max_points).detectAndCompute(img, None)` for 8-bit images, the third detector of the reference's OpenCV
+ * branch (`--detector akaze`, slam/core/features_utils.py:33-55): grey / 255, the nonlinear scale space (Gaussian level 0,
+ * kcontrast as the 70th percentile of the Scharr magnitude, per level the PM-G2 conductivity and the FED cycle of explicit
+ * diffusion steps, halving at a new octave), the scaled-Scharr Hessian determinant, strict 3 x 3 maxima above `threshold`,
+ * suppression across the same and the adjacent levels, the 2-D subpixel refinement, retainBest(max_points) with ties kept
+ * (-1: no cut), the SURF-style main orientation and the full 3-channel M-LDB descriptor: 486 bits in uint8 rows of 61.
+ * tests/akaze_ref.py restates every stage and names what could not be confirmed without cv2 (parity is unpinned); the
+ * kernels equal it bit for bit.
+ * THE DEFINED ARITHMETIC: float32, one IEEE operation at a time; sqrt correctly rounded; cos, sin the float64 function rounded
+ * once; fastAtan2 ORB's polynomial; filter taps ascending through a float32 intermediate; the orientation windows and the
+ * M-LDB cell sums are 64-bit integers at the scale 2^32 (exact and order-free) - stated departures from OpenCV's
+ * build-dependent accumulation.  SUPPRESSION is a predicate: a candidate is dropped iff a candidate of its own or an adjacent
+ * level within its radius (esigma * 1.5, full-resolution pixels) has a larger response, or an equal one and a lower (level,
+ * row, column); OpenCV's scan depends on the order it meets the candidates.
+ * THE ORDER: class_id (the level's index) ascending, then the candidate's row, then its column.
+ * Accepted: descriptor_type 5 (DESCRIPTOR_MLDB), descriptor_size 0, descriptor_channels 3, diffusivity 1 (DIFF_PM_G2) -
+ * anything else is refused with status 2 and a message naming the value, before any HIP call - threshold finite and > 0,
+ * n_octaves 1..8, n_octave_layers 1..8, max_points -1 or 1..2^20, 1 <= max_w, max_h <= 16384.  An octave other than 0 below
+ * 80 x 40 ends the pyramid; a frame without a pixel inside level 0's border (a side <= 10) yields no keypoint; neither is an
+ * error.
+ * CAPACITIES: an instance holds max_candidates candidates (0: one per 8 pixels of max_w x max_h, at least 1024) and
+ * max_keypoints rows (0: one per 16 pixels, at least 1024, or max(4 max_points, 16384) if that is less) - the refined
+ * keypoints before the quota, which bound the rows of every output array.  A frame that exceeds either is VOIDED, never
+ * truncated: the device count is 0, a sticky per-instance word is set (sslam_akaze_overflow: bit 0 candidates, bit 1 rows; it
+ * is never cleared) and the host entry returns 3 with a message that names the counts the frame needed.
+ * DEVICE MEMORY, by arithmetic: 5 float planes per level (Lt, Lflow, Lx, Ly, Ldet; L levels per octave, octaves x 4/3) + 5
+ * full-size temporaries, 20 bytes per candidate and 141 per row: about 0.06 GB at 1241 x 376 and 1.3 GB at 4096 x 2160 with
+ * the defaults.  SSLAM_MAX_IMAGE_H / _W shrink it, as for ORB. */
+typedef struct sslam_akaze sslam_akaze;
+int sslam_akaze_create(sslam_ctx* ctx, int max_w, int max_h, int descriptor_type, int descriptor_size, int descriptor_channels,
+                       double threshold, int n_octaves, int n_octave_layers, int diffusivity, int max_points, int max_candidates,
+                       int max_keypoints, sslam_akaze** out);
+int sslam_akaze_destroy(sslam_akaze* o);
+int sslam_akaze_capacity(sslam_akaze* o, int* rows, int* candidates_or_null);
+int sslam_akaze_overflow(sslam_akaze* o, int* word);     /* the sticky word; synchronises the stream */
+/* img uint8 [h][w][c], c in {1, 3 (BGR), 4 (BGRA)}, w <= max_w and h <= max_h (a larger image is refused, never clipped).
+ * Out, each with `rows` rows of which the first *n_out are written: xy float32 [rows][2]; aux float32 [rows][3] = size,
+ * angle (degrees), response; lvl int32 [rows][2] = octave, class_id; desc uint8 [rows][61], contiguous, nothing written
+ * beyond byte 60 of a row.  Two synchronisations (the count, then the rows). */
+int sslam_akaze_detect_host(sslam_akaze* o, const uint8_t* img, int h, int w, int c, float* xy_out, float* aux_out,
+                            int32_t* lvl_out, uint8_t* desc_out, int32_t* n_out);
+/* Device-pointer variant; enqueue only, no synchronisation.  n_out_dev: device int32[1], the count as sslam_bf_match_dev
+ * reads its m_dev / n_dev; desc_out_dev is its q_dev / t_dev with NORM_HAMMING and D = 61 and xy_out_dev is
+ * sslam_fmat_ransac_dev's xy1 / xy2.  The matcher's row bounds stop at 65536: hand it M = N = min(rows, 65536), as for ORB.
+ * A voided frame writes the count 0. */
+int sslam_akaze_detect_dev(sslam_akaze* o, const uint8_t* img_dev, int h, int w, int c, float* xy_out_dev, float* aux_out_dev,
+                           int32_t* lvl_out_dev, uint8_t* desc_out_dev, int32_t* n_out_dev);
+/* test hooks, after a call.  level_info: info12 = {w, h, levels computed, octaves computed, octave, sigma_size, border, runs in
+ * one workgroup (0 / 1), FED steps into the level, level 0 has an interior (0 / 1), max_candidates, max_keypoints} of a level
+ * of the last frame (w = h = 0 beyond the last).  stage_read, of a frame with an interior; any pointer may be NULL: lt, lflow
+ * (untouched for level 0), lx, ly, ldet float32 [h][w] of the level; of the whole frame: kcontrast8 float32 [8] per octave;
+ * in arrival order cand int32 [max_candidates][4] = level, r, c, response bits; cflag int32 [max_candidates] = 0 suppressed,
+ * 1 a keypoint, 2 survives but the refinement rejects it; kp uint32 [max_keypoints][8] = the float32 bits of x, y, size,
+ * angle, response, then octave, class_id, candidate index (the angle is set for kept rows); kflag int32 [max_keypoints] =
+ * kept by the quota; counts[4] = candidates, keypoints before the quota, output rows, 0. */
+int sslam_akaze_level_info(sslam_akaze* o, int level, int* info12);
+int sslam_akaze_stage_read(sslam_akaze* o, int level, float* lt, float* lflow, float* lx, float* ly, float* ldet, float* kcontrast8,
+                           int32_t* cand, int32_t* cflag, uint32_t* kp, int32_t* kflag, int32_t* counts);
+
 /* ------------------------------------------------------------------ ALIKED
  * Replaces `ALIKED(max_num_keypoints=...).eval().to(device)` at
  * slam/core/features_utils.py:25 and `_bgr_to_tensor` + `detector.extract` +

@@ -112,6 +112,14 @@ def _signatures():
         "sslam_sift_detect_dev": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
         "sslam_sift_octave_info": (i32, [vp, i32, vp]),
         "sslam_sift_stage_read": (i32, [vp, i32, vp, vp, vp, vp, vp, vp]),
+        "sslam_akaze_create": (i32, [vp, i32, i32, i32, i32, i32, C.c_double, i32, i32, i32, i32, i32, i32, c_void_pp]),
+        "sslam_akaze_destroy": (i32, [vp]),
+        "sslam_akaze_capacity": (i32, [vp, c_int_p, c_int_p]),
+        "sslam_akaze_overflow": (i32, [vp, c_int_p]),
+        "sslam_akaze_detect_host": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "sslam_akaze_detect_dev": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "sslam_akaze_level_info": (i32, [vp, i32, vp]),
+        "sslam_akaze_stage_read": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "sslam_aliked_create": (i32, [vp, vp, sz, i32, i32, i32, c_void_pp]),
         "sslam_aliked_create_batched": (i32, [vp, vp, sz, i32, i32, i32, i32, c_void_pp]),
         "sslam_aliked_extract_batch_dev": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]),

@@ -4,7 +4,7 @@ Stands in for `cv2.BFMatcher(normType, crossCheck)` as the reference's default c
 (`--detector orb --matcher bf`): `_get_opencv_matcher` builds `cv2.BFMatcher(norm, crossCheck=True)` with NORM_HAMMING for
 ORB / AKAZE and NORM_L2 for SIFT (slam/core/features_utils.py:54-55) and `feature_matcher` calls `.match(des0, des1)` on it
 and sorts the result by `.distance` (:173-178).  `BFMatcher(norm, crossCheck=True)` here is that object: hand it to
-`feature_matcher` as the matcher.  The detectors that make ORB / SIFT / AKAZE descriptors still need OpenCV.
+`feature_matcher` as the matcher.  The detectors that make ORB / SIFT / AKAZE descriptors have GPU forms too (orb.py, sift.py, akaze.py); only FLANN still needs OpenCV.
 
 Only `match` is provided (one nearest neighbour, optionally cross-checked): no `knnMatch` with k > 1, no `radiusMatch`, no
 NORM_L1 / NORM_HAMMING2, no train collections, no mask.  Semantics: include/sslam_hip.h, `sslam_bf_match_host`.
