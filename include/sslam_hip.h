@@ -460,6 +460,45 @@ int sslam_bf_match_dev(sslam_ctx* ctx, int norm, int cross_check, int D, const v
                        const void* t_dev, int N, const int32_t* n_dev, int32_t* ij_out_dev, float* dist_out_dev,
                        int32_t* info_out_dev);
 
+/* k nearest neighbours: `cv2.BFMatcher(norm).knnMatch(des0, des1, k)` without crossCheck, k = 1..8 (anything else is
+ * refused).  norm, D, M, N, the distances and their limits are those of sslam_bf_match_host: the kernels share one
+ * arithmetic chain (csrc/bf_tile.hpp), so a distance here has the bits it has there.
+ *   The neighbours of query row i are its valid train rows (d < FLT_MAX; a NaN never is) in ascending order of the key
+ *   (float32 d, train index) - the lower index first on a tie -, the first min(k, number of valid rows) of them.  The order
+ *   is total: the result does not depend on `splits`, and is bitwise the same from run to run.
+ *   idx_out[M][k] int32, padded with -1;  dist_out[M][k] float32, padded with +inf;  cnt_out[M] int32 neighbours per row
+ *   splits : the train tiles (64 rows each) of a row tile are shared out among this many workgroups.  0: chosen by the
+ *            host plan (csrc/bf_knn_plan.hpp) so that the grid fills the device about twice; 1..ceil(N / 64) is honoured;
+ *            anything else is refused
+ *   M == 0: nothing is written.  N == 0: every row gets cnt 0 and the padding, no device work.
+ * The M x N distances are never stored.  Scratch: 8 * splits * M * K bytes of the context's buffer, K the smallest of
+ * 2 / 4 / 8 that is >= k.  Not built: k > 8, masks, radiusMatch, train collections, NORM_L1 / NORM_HAMMING2 / NORM_L2SQR. */
+int sslam_bf_knn_match_host(sslam_ctx* ctx, int norm, int D, const void* q, int M, const void* t, int N, int k, int splits,
+                            int32_t* idx_out, float* dist_out, int32_t* cnt_out);
+/* Device-pointer variant; enqueue only (no allocation, no synchronisation).  m_dev / n_dev as for sslam_bf_match_dev:
+ * clamped to [0, bound], negative = empty, rows beyond the counts are never read.  Rows of the outputs at and beyond the
+ * device count m are NOT written.
+ *   idx_out_dev[M][k], dist_out_dev[M][k], cnt_out_dev[M];  info_out_dev[4] int32 = {m, n, k, splits used}
+ * The context's scratch buffer is (re)allocated when splits * M * K grows: call once with the largest bounds before capturing
+ * or pipelining. */
+int sslam_bf_knn_match_dev(sslam_ctx* ctx, int norm, int D, const void* q_dev, int M, const int32_t* m_dev,
+                           const void* t_dev, int N, const int32_t* n_dev, int k, int splits, int32_t* idx_out_dev,
+                           float* dist_out_dev, int32_t* cnt_out_dev, int32_t* info_out_dev);
+
+/* Lowe's ratio test on the two nearest neighbours: query row i is kept iff it has two neighbours and
+ * (double)d1 < ratio * (double)d2 - ONE fp64 multiply, bit for bit Python's `m.distance < ratio * n.distance` on the
+ * DMatch floats of knnMatch(k = 2); an equality is dropped.  ratio must be finite and > 0.
+ *   ij_out[M][2] int32 (queryIdx, trainIdx of the nearest), ascending queryIdx;  dist_out[M] float32 = d1;  k_out: the count
+ * splits, limits and scratch (K = 2) as for sslam_bf_knn_match_host. */
+int sslam_bf_ratio_match_host(sslam_ctx* ctx, int norm, int D, const void* q, int M, const void* t, int N, double ratio,
+                              int splits, int32_t* ij_out, float* dist_out, int32_t* k_out);
+/* Device-pointer variant; enqueue only.  The outputs have the layout sslam_bf_match_dev leaves - ij_out_dev[M][2],
+ * dist_out_dev[M], info_out_dev[4] = {K, m, n, 0} -, so ij_out_dev and info_out_dev are what sslam_fmat_ransac_dev takes as
+ * ij_dev / n_dev with nothing read back in between. */
+int sslam_bf_ratio_match_dev(sslam_ctx* ctx, int norm, int D, const void* q_dev, int M, const int32_t* m_dev,
+                             const void* t_dev, int N, const int32_t* n_dev, double ratio, int splits, int32_t* ij_out_dev,
+                             float* dist_out_dev, int32_t* info_out_dev);
+
 /* ----------------------------------------------------------------------- ORB
  * Replaces `cv2.ORB_create(nfeatures, scaleFactor, nlevels, edgeThreshold, 0, 2, scoreType, 31, fastThreshold)
  * .detectAndCompute(img, None)` for 8-bit images, the detector of the reference's default configuration

@@ -96,6 +96,10 @@ def _signatures():
                                                     C.c_double, vp, vp, vp, vp]),
         "sslam_bf_match_host": (i32, [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp]),
         "sslam_bf_match_dev": (i32, [vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]),
+        "sslam_bf_knn_match_host": (i32, [vp, i32, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp]),
+        "sslam_bf_knn_match_dev": (i32, [vp, i32, i32, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]),
+        "sslam_bf_ratio_match_host": (i32, [vp, i32, i32, vp, i32, vp, i32, C.c_double, i32, vp, vp, vp]),
+        "sslam_bf_ratio_match_dev": (i32, [vp, i32, i32, vp, i32, vp, vp, i32, vp, C.c_double, i32, vp, vp, vp]),
         "sslam_orb_create": (i32, [vp, i32, i32, i32, C.c_double, i32, i32, i32, i32, vp, c_void_pp]),
         "sslam_orb_destroy": (i32, [vp]),
         "sslam_orb_capacity": (i32, [vp, c_int_p]),

@@ -29,118 +29,36 @@
 // The L2 inner loop is plain fp32 VALU on purpose, no matrix core: the arithmetic above is the contract.  (The compiler pairs
 // the subtracts and the fmas of two pairs into v_pk_add_f32 / v_pk_fma_f32 - each half one IEEE operation, the same bits -
 // and the build's ISA guard checks that none has the op_sel form it bars.)
-#include "common.hpp"
+#include "bf_tile.hpp"
 #include "geom_common.hpp"
-
-#include <cfloat>
 
 namespace {
 
-constexpr int BF_NORM_L2 = 4, BF_NORM_HAMMING = 6;      // cv2's values
-constexpr int BF_MAX_ROWS = 65536;
-constexpr int BF_MAX_D_HAMMING = 256, BF_MAX_D_L2 = 512;
-constexpr int BF_T = 256;                // the distance workgroup: 16 x 16 threads, 4 x 4 pairs each
-constexpr int BF_TILE = 64;              // rows of a tile, both sides
-constexpr int BF_KC = 32;                // elements of a row per staged chunk
-constexpr int BF_LD = BF_TILE + 4;       // leading dimension of a staged chunk [k][row]: rows of 272 bytes (16-byte aligned)
-constexpr int BF_FIN_T = 1024;
-constexpr unsigned long long BF_NONE = ~0ull;
+using namespace sslam::bf;               // the limits, the norms and the tile loop: bf_tile.hpp, shared with bf_knn_kernels.hip
 
-struct BFArgs {
-    int D;                                    // bytes (Hamming) or floats (L2) per row
-    int M, N;                                 // row bounds
-    const int32_t* m_dev; const int32_t* n_dev;   // device counts, clamped to [0, bound]; may be NULL
-    const void* q; const void* t;             // [M][D], [N][D]
+constexpr int BF_FIN_T = 1024;
+
+struct BFArgs : BFRows {
     int cross_check;
-    int words_ok;                             // Hamming: D % 4 == 0 and both bases 4-byte aligned: rows are read as words
     unsigned long long* best_q;               // [M] min over the trains of (bits(d) << 32 | train)
     unsigned long long* best_t;               // [N] min over the queries of (bits(d) << 32 | query)
     int32_t* ij_out; float* dist_out; int32_t* info_out;
 };
 
-__device__ __forceinline__ int bf_count(const int32_t* dev, int bound) { return dev ? min(max(dev[0], 0), bound) : bound; }
-
-struct HammingNorm {
-    using Elem = uint32_t;                    // a staged element: 4 bytes of the row, zero beyond D
-    static __device__ __forceinline__ int elems(int D) { return (D + 3) >> 2; }
-    static __device__ __forceinline__ Elem load(const BFArgs& a, const void* base, int row, int k) {
-        if (a.words_ok) return reinterpret_cast<const uint32_t*>(base)[(size_t)row * (a.D >> 2) + k];
-        const uint8_t* p = reinterpret_cast<const uint8_t*>(base) + (size_t)row * a.D;
-        uint32_t w = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-            if (4 * k + b < a.D) w |= (uint32_t)p[4 * k + b] << (8 * b);
-        return w;
-    }
-    static __device__ __forceinline__ void step(Elem& acc, Elem x, Elem y) { acc += __popc(x ^ y); }
-    static __device__ __forceinline__ float finish(Elem acc) { return (float)acc; }
-};
-
-struct L2Norm {
-    using Elem = float;
-    static __device__ __forceinline__ int elems(int D) { return D; }
-    static __device__ __forceinline__ Elem load(const BFArgs& a, const void* base, int row, int k) {
-        return reinterpret_cast<const float*>(base)[(size_t)row * a.D + k];
-    }
-    static __device__ __forceinline__ void step(Elem& acc, Elem x, Elem y) {
-        const float diff = x - y;
-        acc = __builtin_fmaf(diff, diff, acc);
-    }
-    static __device__ __forceinline__ float finish(Elem acc) { return __fsqrt_rn(acc); }
-};
-
-template <class E>
-struct alignas(16) BFVec4 { E v[4]; };
-
-__device__ __forceinline__ unsigned long long bf_min(unsigned long long x, unsigned long long y) { return x < y ? x : y; }
-
 // ---- 1. a 64 x 64 tile of pairs per workgroup: the minimum key of every row and of every column of the tile ----------
 template <class Norm>
 __global__ __launch_bounds__(BF_T) void bf_distance_kernel(BFArgs a) {
     using Elem = typename Norm::Elem;
-    __shared__ BFVec4<Elem> sq4[BF_KC * BF_LD / 4], st4[BF_KC * BF_LD / 4];
+    __shared__ BFVec4<Elem> sq4[BF_STAGE_VEC4], st4[BF_STAGE_VEC4];
     __shared__ unsigned long long s_row[BF_TILE], s_col[BF_TILE];
-    Elem* sq = &sq4[0].v[0];
-    Elem* st = &st4[0].v[0];
     const int m = bf_count(a.m_dev, a.M), n = bf_count(a.n_dev, a.N);
     const int q0 = blockIdx.y * BF_TILE, t0 = blockIdx.x * BF_TILE;
     if (q0 >= m || t0 >= n) return;          // (the whole workgroup: the counts are uniform)
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    if (tid < BF_TILE) { s_row[tid] = BF_NONE; s_col[tid] = BF_NONE; }       // (ordered by the first barrier below: E >= 1)
+    if (tid < BF_TILE) { s_row[tid] = BF_NONE; s_col[tid] = BF_NONE; }       // (ordered by the tile loop's first barrier: E >= 1)
 
     Elem acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0;
-
-    const int E = Norm::elems(a.D);
-    for (int k0 = 0; k0 < E; k0 += BF_KC) {
-        const int kn = min(BF_KC, E - k0);
-        // stage [kn][64] of both sides: a turn covers 8 k x 32 rows, 8 lanes along k (32 contiguous bytes of a row) and a
-        // 32-lane group on 32 different banks (bank = 4 k + row).  Rows beyond the counts are zeros and are left out below.
-#pragma unroll
-        for (int s = 0; s < BF_TILE * BF_KC / BF_T; ++s) {
-            const int k = (tid & 7) + 8 * (s & 3), r = (tid >> 3) + 32 * (s >> 2);
-            if (8 * (s & 3) >= kn) continue;
-            Elem x = 0, y = 0;
-            if (k < kn) {
-                if (q0 + r < m) x = Norm::load(a, a.q, q0 + r, k0 + k);
-                if (t0 + r < n) y = Norm::load(a, a.t, t0 + r, k0 + k);
-            }
-            sq[k * BF_LD + r] = x;
-            st[k * BF_LD + r] = y;
-        }
-        __syncthreads();
-        for (int k = 0; k < kn; ++k) {
-            const BFVec4<Elem> x = sq4[(k * BF_LD + 4 * ty) / 4], y = st4[(k * BF_LD + 4 * tx) / 4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) Norm::step(acc[i][j], x.v[i], y.v[j]);
-        }
-        __syncthreads();
-    }
+    bf_tile_distances<Norm>(a, q0, t0, m, n, sq4, st4, acc);
 
     unsigned long long rk[4] = {BF_NONE, BF_NONE, BF_NONE, BF_NONE}, ck[4] = {BF_NONE, BF_NONE, BF_NONE, BF_NONE};
 #pragma unroll
@@ -150,9 +68,8 @@ __global__ __launch_bounds__(BF_T) void bf_distance_kernel(BFArgs a) {
             const float d = Norm::finish(acc[i][j]);
             const int qi = q0 + 4 * ty + i, tj = t0 + 4 * tx + j;
             if (qi < m && tj < n && d < FLT_MAX) {                          // (NaN fails the comparison)
-                const unsigned long long hi = (unsigned long long)__float_as_uint(d) << 32;
-                rk[i] = bf_min(rk[i], hi | (unsigned)tj);
-                ck[j] = bf_min(ck[j], hi | (unsigned)qi);
+                rk[i] = bf_min(rk[i], bf_key(d, tj));
+                ck[j] = bf_min(ck[j], bf_key(d, qi));
             }
         }
     // a row's 16 threads are 16 adjacent lanes; a column's 16 threads are 4 lanes (16 apart) of each of the 4 waves
@@ -222,21 +139,6 @@ int bf_enqueue(hipStream_t s, const BFArgs& a, int norm) {
     SSLAM_HIP_CHECK(hipGetLastError());
     return 0;
 }
-
-// every refusal that needs no device, in the order of the arguments
-int bf_check(const char* who, sslam_ctx* ctx, int norm, int D, int M, int N) {
-    SSLAM_REQUIRE(ctx != nullptr, "%s: ctx is NULL", who);
-    SSLAM_REQUIRE(norm == BF_NORM_L2 || norm == BF_NORM_HAMMING,
-                  "%s: norm %d is neither NORM_L2 (4) nor NORM_HAMMING (6)", who, norm);
-    const int dmax = norm == BF_NORM_HAMMING ? BF_MAX_D_HAMMING : BF_MAX_D_L2;
-    SSLAM_REQUIRE(D >= 1 && D <= dmax, "%s: D %d outside 1..%d (%s)", who, D, dmax,
-                  norm == BF_NORM_HAMMING ? "bytes per row, NORM_HAMMING" : "floats per row, NORM_L2");
-    SSLAM_REQUIRE(M >= 0 && M <= BF_MAX_ROWS, "%s: M %d outside 0..%d", who, M, BF_MAX_ROWS);
-    SSLAM_REQUIRE(N >= 0 && N <= BF_MAX_ROWS, "%s: N %d outside 0..%d", who, N, BF_MAX_ROWS);
-    return 0;
-}
-
-size_t bf_row_bytes(int norm, int D) { return norm == BF_NORM_HAMMING ? (size_t)D : (size_t)D * sizeof(float); }
 
 // the slab-backed pointers of BFArgs, in slab order.  host: the inputs and outputs are the slab's too
 void bf_bind(sslam::Slab& sl, BFArgs& a, size_t row_bytes, bool host) {
