@@ -672,6 +672,32 @@ int sslam_akaze_level_info(sslam_akaze* o, int level, int* info12);
 int sslam_akaze_stage_read(sslam_akaze* o, int level, float* lt, float* lflow, float* lx, float* ly, float* ldet, float* kcontrast8,
                            int32_t* cand, int32_t* cflag, uint32_t* kp, int32_t* kflag, int32_t* counts);
 
+/* ------------------------------------------------------ keyframe thumbnails
+ * Replaces `cv2.resize(bgr, hw)` + `cv2.imencode('.jpg', th, [cv2.IMWRITE_JPEG_QUALITY, q])` of `make_thumb`
+ * (slam/core/keyframe_utils.py:26-30): cv2.resize for uint8 / INTER_LINEAR in OpenCV's fixed-point form, libjpeg's integer
+ * Y Cb Cr and 4:2:0 subsampling, an exactly defined integer forward DCT and quantisation with libjpeg's tables for the quality,
+ * baseline Huffman coding with the Annex K tables, byte stuffing and the JFIF header - all on the device, eight launches on the
+ * context's stream.  A one-channel source gives a one-component JPEG, 3 or 4 channels (B G R [A], alpha dropped) Y Cb Cr.
+ * Parity with cv2 itself is unpinned (tests/thumb_ref.py names what could not be confirmed).
+ * One instance serves one thumbnail size and quality and any source up to max_src_w x max_src_h.  Refused with a message naming
+ * the value, before any device call: quality outside 1..100, a thumbnail side outside 1..4096, a source side outside 1..16384 or
+ * larger than the instance's, C not in {1, 3, 4}. */
+typedef struct sslam_thumb sslam_thumb;
+int sslam_thumb_create(sslam_ctx* ctx, int max_src_w, int max_src_h, int dst_w, int dst_h, int quality, sslam_thumb** out);
+int sslam_thumb_destroy(sslam_thumb* t);
+/* bytes no encode of this instance can exceed: header + 416 per block (20 + 63 * 26 bits, every byte stuffed) + 2 */
+int sslam_thumb_capacity(sslam_thumb* t, int* capacity);
+/* src uint8 [Hs][Ws][C] (host) -> the JPEG stream in out[0 .. *nbytes) (host, cap bytes; sslam_thumb_capacity always suffices) */
+int sslam_thumb_encode_host(sslam_thumb* t, const uint8_t* src, int Hs, int Ws, int C, uint8_t* out, int cap, int* nbytes);
+/* device pointers; enqueue only: out_dev holds sslam_thumb_capacity bytes, the int32 byte count is left at nbytes_dev */
+int sslam_thumb_encode_dev(sslam_thumb* t, const uint8_t* src_dev, int Hs, int Ws, int C, uint8_t* out_dev, int32_t* nbytes_dev);
+/* the resize alone: dst uint8 [dst_h][dst_w][C] (host), every channel interpolated */
+int sslam_thumb_resize_host(sslam_thumb* t, const uint8_t* src, int Hs, int Ws, int C, uint8_t* dst);
+/* for tests, of the LAST encode (synchronises).  which: 0 the resized image uint8 [dst_h][dst_w][C] (computed now, from the last
+ * encode's source, which must still be alive); 1 Y uint8 [yh][yw] padded to the MCU multiple; 2 / 3 Cb / Cr uint8 [yh/2][yw/2];
+ * 4 coefficients int16 [blocks][64], zigzag order, blocks in scan order; 5 bit offsets uint32 [blocks] */
+int sslam_thumb_stage_read(sslam_thumb* t, int which, void* dst);
+
 /* ------------------------------------------------------------------ ALIKED
  * Replaces `ALIKED(max_num_keypoints=...).eval().to(device)` at
  * slam/core/features_utils.py:25 and `_bgr_to_tensor` + `detector.extract` +

@@ -124,6 +124,13 @@ def _signatures():
         "sslam_akaze_detect_dev": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
         "sslam_akaze_level_info": (i32, [vp, i32, vp]),
         "sslam_akaze_stage_read": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sslam_thumb_create": (i32, [vp, i32, i32, i32, i32, i32, c_void_pp]),
+        "sslam_thumb_destroy": (i32, [vp]),
+        "sslam_thumb_capacity": (i32, [vp, c_int_p]),
+        "sslam_thumb_encode_host": (i32, [vp, vp, i32, i32, i32, vp, i32, c_int_p]),
+        "sslam_thumb_encode_dev": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+        "sslam_thumb_resize_host": (i32, [vp, vp, i32, i32, i32, vp]),
+        "sslam_thumb_stage_read": (i32, [vp, i32, vp]),
         "sslam_aliked_create": (i32, [vp, vp, sz, i32, i32, i32, c_void_pp]),
         "sslam_aliked_create_batched": (i32, [vp, vp, sz, i32, i32, i32, i32, c_void_pp]),
         "sslam_aliked_extract_batch_dev": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
