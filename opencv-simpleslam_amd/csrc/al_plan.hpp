@@ -19,6 +19,7 @@ constexpr int DCN3_CS = 1;            // workgroups per pixel tile of the 1/8 de
 constexpr int DCN4_CS = 4;            // ... and of the 1/32 ones (output channels split: 10 tiles per frame there)
 constexpr int AGG_PRE = 13;           // al_agg_pre_kernel: planes per level (8 projections + S, H, V, D1, D2)
 constexpr int ST_W = 32, ST_H = 8;    // al_score_tail_kernel: output tile
+constexpr int PRE_LDS_MAX = 48 * 1024;  // al_preprocess_kernel: most LDS bytes a tile may take (three workgroups per CU at least)
 constexpr int NHALO = 10;             // dependency radius of simple_nms: 2 + 4 + 4
 constexpr int NW_R = 48, NW_OW = 64 - 2 * NHALO, NW_OH = NW_R - 2 * NHALO;      // al_nms_wave_kernel: rows held, output tile
 constexpr int HBINS = 4096;           // score histogram bins (uniform in score, monotone)
@@ -63,6 +64,10 @@ struct ALPlan {
     int npx, collect_gx;
     ALAggTile agg_tile;
     float scale_x, scale_y;             // network pixels per input pixel
+    // al_preprocess_kernel: a workgroup owns pre_tw x pre_th pixels of the padded image (pre_tw a power of two) and keeps the
+    // horizontally blurred source span they read in LDS: at most pre_cols columns x pre_rows rows per channel, beside the raw
+    // bytes of those rows (pre_raw bytes per row) and the 256 floats of b / 255
+    int pre_tw, pre_th, pre_gx, pre_gy, pre_cols, pre_rows, pre_raw, pre_lds;
 };
 
 inline ALPlan al_plan(int H, int W, int C, int F) {
@@ -132,6 +137,24 @@ inline ALPlan al_plan(int H, int W, int C, int F) {
     //  bit-identical)
     p.agg_tile = F >= 4 ? ALAggTile::T64x128 : ALAggTile::T64x64;
     p.scale_x = (float)d.w / (float)W; p.scale_y = (float)d.h / (float)H;
+    // pre-processing: the largest tile of the ladder whose source span fits PRE_LDS_MAX.  Neighbouring network pixels are fx (fy)
+    // source pixels apart and a pixel reads source columns x0 and x0 + 1, so tw pixels span at most fx (tw - 1) + 3 columns (one
+    // more here for the rounding of the device's fp32 coordinates), rows the same plus the vertical taps either side; the raw rows
+    // carry the horizontal taps either side, C bytes a pixel, whole dwords from an aligned address.  The last tile, 4 x 1, takes
+    // 35 KB at 31 taps (fx = fy = 17, C = 4): every size al_refusal admits fits
+    {
+        static constexpr int ladder[][2] = {{64, 8}, {32, 8}, {32, 4}, {16, 4}, {16, 2}, {8, 2}, {8, 1}, {4, 1}};
+        const int rx = p.blur ? p.kx / 2 : 0, ry = p.blur ? p.ky / 2 : 0, planes = C == 1 ? 1 : 3;
+        for (const auto& t : ladder) {
+            p.pre_tw = t[0]; p.pre_th = t[1];
+            p.pre_cols = (int)(fx * (t[0] - 1)) + 4;
+            p.pre_rows = (int)(fy * (t[1] - 1)) + 4 + 2 * ry;
+            p.pre_raw = ((p.pre_cols + 2 * rx) * C + 3) / 4 * 4 + 4;
+            p.pre_lds = 256 * 4 + planes * p.pre_rows * p.pre_cols * 4 + p.pre_rows * p.pre_raw;
+            if (p.pre_lds <= PRE_LDS_MAX) break;
+        }
+        p.pre_gx = al_cdiv(Wp, p.pre_tw); p.pre_gy = al_cdiv(Hp, p.pre_th);
+    }
     return p;
 }
 

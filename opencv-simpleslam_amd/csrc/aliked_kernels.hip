@@ -133,69 +133,170 @@ struct FrameOut { float* xy[MAX_FRAMES]; float* desc[MAX_FRAMES]; float* score[M
 // ------------------------------------------------------------------------ //
 //  0. pre-processing: u8 HWC (BGR | gray | BGRA) -> RGB/255 -> [blur] -> resize -> pad
 // ------------------------------------------------------------------------ //
-__global__ void al_to_float_kernel(FrameIn srcs, float* __restrict__ dst, Dims d,
-                                   const float* __restrict__ gx, int kx, int blur, size_t fs) {
-    // dst [3][H][W] = horizontally blurred RGB/255 (reflect border), or plain RGB/255
-    const uint8_t* __restrict__ src = srcs.img[blockIdx.z];
-    dst = fsh(dst, blockIdx.z, fs);
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= d.W) return;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int sc = d.C == 1 ? 0 : 2 - c;                      // BGR -> RGB
-        float v;
-        if (!blur) {
-            v = (float)src[((size_t)y * d.W + x) * d.C + sc] / 255.0f;
-        } else {
-            v = 0.0f;
-            const int r = kx / 2;
-#pragma unroll 8            // (rolled, every tap waited for its own byte load)
-            for (int k = 0; k < kx; ++k) {
-                int xx = x + k - r;
-                xx = xx < 0 ? -xx : (xx >= d.W ? 2 * d.W - 2 - xx : xx);       // reflect
-                v += gx[k] * ((float)src[((size_t)y * d.W + xx) * d.C + sc] / 255.0f);
-            }
-        }
-        dst[((size_t)c * d.H + y) * d.W + x] = v;
-    }
+// One kernel, separable (r31; the two-launch form it replaces wrote the horizontally blurred float image [3][H][W] to memory and
+// read it back with 4 ky scattered loads per output and channel, its first pass fetching every tap as a byte at stride C).  A
+// workgroup owns a tile of the padded output and holds in LDS what the tile reads:
+//   1. the source rows of its span as whole dwords from 4-byte aligned addresses (`raw`; a row of an odd W C starts anywhere);
+//   2. their horizontal blur as RGB/255, BGR -> RGB and the reflect border applied while reading `raw`; plain RGB/255 without blur.
+//      LDS row j is the source row reflect(ylo + j): a row the border folds onto is computed twice rather than indexed twice;
+//   3. per output pixel the vertical taps, the bilinear mix and the replicate pad, from LDS.
+// Values are the two-launch form's bit for bit: taps ascending, v = fma(g, value, v); value = b / 255 (a correctly rounded division,
+// here taken once per byte value into `tab`); and the mix with the contractions the compiler had chosen there written out -
+// fma(lx, v01, hx v00), fma(hx, v10, lx v11), and hy top + ly bot with no contraction.
+struct PreTile { int tw, th, cols, rows, raw; };     // ALPlan::pre_*
+__device__ __forceinline__ int al_reflect(int i, int n) {
+    i = i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i);
+    return min(max(i, 0), n - 1);                   // (a no-op wherever the blur radius is below n: every admitted size)
 }
-
-__global__ void al_resize_pad_kernel(const float* __restrict__ src, float* __restrict__ img, Dims d,
-                                     const float* __restrict__ gy, int ky, int blur, size_t fs) {
-    // img [3][Hp][Wp]: replicate-padded bilinear (align_corners=False) resize of (vertically blurred) src
-    const Tile3 tb = xcd_band();                    // (the vertical taps and the bilinear rows of neighbouring output rows overlap)
-    src = fsh(src, tb.z, fs); img = fsh(img, tb.z, fs);
-    const int xp = tb.x * blockDim.x + threadIdx.x, yp = tb.y;
-    if (xp >= d.Wp) return;
-    const int y = min(max(yp - d.pt, 0), d.h - 1), x = min(max(xp - d.pl, 0), d.w - 1);
+// network pixel o of an axis -> the two source pixels it mixes and the weight of the second (align_corners=False)
+__device__ __forceinline__ void al_src_pos(int o, int n_in, float s, int& i0, int& i1, float& l) {
+    float f = fmaf(s, __fadd_rn((float)o, 0.5f), -0.5f);
+    f = f < 0.0f ? 0.0f : f;
+    i0 = (int)f; i1 = i0 + (i0 < n_in - 1); l = __fsub_rn(f, (float)i0);
+}
+__global__ __launch_bounds__(256) void al_preprocess_kernel(FrameIn srcs, float* __restrict__ img, Dims d, const float* __restrict__ gk,
+                                                            int kx, int ky, int blur, PreTile t, size_t fs) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char pre_lds[];
+    const Tile3 tb = xcd_band();                    // (the spans of neighbouring tiles overlap)
+    const uint8_t* __restrict__ src = srcs.img[tb.z];
+    img = fsh(img, tb.z, fs);
+    const int planes = d.C == 1 ? 1 : 3;
+    float* tab = reinterpret_cast<float*>(pre_lds);                 // [256] b / 255
+    float* hb = tab + 256;                                          // [planes][t.rows][t.cols]
+    uint8_t* raw = reinterpret_cast<uint8_t*>(hb + planes * t.rows * t.cols);      // [t.rows][t.raw]
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const float sy_ = (float)d.H / (float)d.h, sx_ = (float)d.W / (float)d.w;
-    float fy = sy_ * ((float)y + 0.5f) - 0.5f, fx = sx_ * ((float)x + 0.5f) - 0.5f;
-    fy = fy < 0.0f ? 0.0f : fy;
-    fx = fx < 0.0f ? 0.0f : fx;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < d.H - 1), x1 = x0 + (x0 < d.W - 1);
-    const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.0f - ly, hx = 1.0f - lx;
+    const int rx = blur ? kx / 2 : 0, ry = blur ? ky / 2 : 0;
+    // the tile's span: source positions are monotone in the output pixel, so the first and the last pixel bound it
+    const int xp_a = tb.x * t.tw, yp_a = tb.y * t.th;
+    const int xp_b = min(xp_a + t.tw, d.Wp) - 1, yp_b = min(yp_a + t.th, d.Hp) - 1;
+    int xlo, xhi, ylo, yhi, unused; float unused_l;
+    al_src_pos(min(max(xp_a - d.pl, 0), d.w - 1), d.W, sx_, xlo, unused, unused_l);
+    al_src_pos(min(max(xp_b - d.pl, 0), d.w - 1), d.W, sx_, unused, xhi, unused_l);
+    al_src_pos(min(max(yp_a - d.pt, 0), d.h - 1), d.H, sy_, ylo, unused, unused_l);
+    al_src_pos(min(max(yp_b - d.pt, 0), d.h - 1), d.H, sy_, unused, yhi, unused_l);
+    ylo -= ry; yhi += ry;
+    const int ncols = min(xhi - xlo + 1, t.cols), nrows = min(yhi - ylo + 1, t.rows);      // (the plan's bounds hold: al_plan.hpp)
+    const int rlo = max(xlo - rx, 0), rhi = min(xhi + rx, d.W - 1);                          // raw columns: a reflected tap lands inside
+    const int raw_bytes = (rhi - rlo + 1) * d.C;
+    const uint8_t* const src_end = src + (size_t)d.H * d.W * d.C;
+
+    tab[tid] = (float)tid / 255.0f;
+    // 1. raw rows: a wave per row, a lane per dword
+    for (int j = wv; j < nrows; j += 4) {
+        const uint8_t* p = src + ((size_t)al_reflect(ylo + j, d.H) * d.W + rlo) * d.C;
+        const int shift = (int)(reinterpret_cast<uintptr_t>(p) & 3u);
+        p -= shift;
+        const int ndw = min((shift + raw_bytes + 3) >> 2, t.raw >> 2);
+        uint32_t* row = reinterpret_cast<uint32_t*>(raw + j * t.raw);
+        for (int i = lane; i < ndw; i += 64) {
+            const uint8_t* q = p + 4 * i;
+            uint32_t v;
+            if (q >= src && q + 4 <= src_end) {
+                v = *reinterpret_cast<const uint32_t*>(q);
+            } else {                                // the dword straddles an end of the image: only the bytes inside it
+                v = 0;
+                for (int b = 0; b < 4; ++b)
+                    if (q + b >= src && q + b < src_end) v |= (uint32_t)q[b] << (8 * b);
+            }
+            row[i] = v;
+        }
+    }
+    __syncthreads();
+    // 2. horizontal pass: elements (row j, column i) dealt 256 apart, stepped without a division per element
+    {
+        const float* __restrict__ gx = gk;
+        const int step_j = 256 / ncols, step_i = 256 - step_j * ncols;
+        int j = tid / ncols, i = tid - j * ncols;
+        const unsigned src_lo = (unsigned)reinterpret_cast<uintptr_t>(src);
+        const int plane = t.rows * t.cols;
+        while (j < nrows) {
+            // (the row's first byte inside its first dword, as in 1.; an image is below 4 GB)
+            const unsigned shift = (src_lo + (unsigned)((al_reflect(ylo + j, d.H) * d.W + rlo) * d.C)) & 3u;
+            const uint8_t* row = raw + j * t.raw + shift - rlo * d.C;
+            float* o = hb + j * t.cols + i;
+            const int x = xlo + i;
+            // a tap's column once, its bytes (B, G, R side by side) for the three planes: R = byte 2 first (BGR -> RGB)
+            if (planes == 1) {
+                float v = 0.0f;
+                if (!blur) v = tab[row[x * d.C]];
+                else
+#pragma unroll 4
+                    for (int k = 0; k < kx; ++k) v = fmaf(gx[k], tab[row[min(max(al_reflect(x + k - rx, d.W), rlo), rhi) * d.C]], v);
+                o[0] = v;
+            } else {
+                float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
+                if (!blur) {
+                    const uint8_t* px = row + x * d.C;
+                    v0 = tab[px[2]]; v1 = tab[px[1]]; v2 = tab[px[0]];
+                } else {
+#pragma unroll 4
+                    for (int k = 0; k < kx; ++k) {
+                        const uint8_t* px = row + min(max(al_reflect(x + k - rx, d.W), rlo), rhi) * d.C;
+                        const float g = gx[k];
+                        v0 = fmaf(g, tab[px[2]], v0); v1 = fmaf(g, tab[px[1]], v1); v2 = fmaf(g, tab[px[0]], v2);
+                    }
+                }
+                o[0] = v0; o[plane] = v1; o[2 * plane] = v2;
+            }
+            j += step_j; i += step_i;
+            if (i >= ncols) { i -= ncols; ++j; }
+        }
+    }
+    __syncthreads();
+    // 3. vertical taps, bilinear mix, replicate pad: t.tw a power of two, thread = (column, row mod 256 / tw)
+    {
+        const float* __restrict__ gy = gk + 32;
+        const int sh = __ffs(t.tw) - 1, xp = xp_a + (tid & (t.tw - 1));
+        if (xp >= d.Wp) return;
+        int x0, x1; float lx;
+        al_src_pos(min(max(xp - d.pl, 0), d.w - 1), d.W, sx_, x0, x1, lx);
+        const float hx = __fsub_rn(1.0f, lx);
+        // x1 is x0 or x0 + 1 and y1 is y0 or y0 + 1 (the same at the image's last column / row): a pixel reads the LDS rows
+        // y0 .. y0 + ky once each, columns x0 and x0 + 1 as a pair, and selects - a third of the reads of four separate taps.
+        // (At the last row / column the pair or the row past the taps holds something else, inside the allocation, and is not selected.)
+        const bool dx = x1 != x0;
+        x0 -= xlo;
+        for (int ty = tid >> sh; ty < t.th; ty += 256 >> sh) {
+            const int yp = yp_a + ty;
+            if (yp >= d.Hp) break;
+            int y0, y1; float ly;
+            al_src_pos(min(max(yp - d.pt, 0), d.h - 1), d.H, sy_, y0, y1, ly);
+            const float hy = __fsub_rn(1.0f, ly);
+            const bool dy = y1 != y0;
+            const float* p = hb + (y0 - ylo - ry) * t.cols + x0;         // LDS row of tap k of y0: k rows on
+            float out = 0.0f;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float* p = src + (size_t)c * d.H * d.W;
-        float v00, v01, v10, v11;
-        if (!blur) {
-            v00 = p[(size_t)y0 * d.W + x0]; v01 = p[(size_t)y0 * d.W + x1];
-            v10 = p[(size_t)y1 * d.W + x0]; v11 = p[(size_t)y1 * d.W + x1];
-        } else {
-            v00 = v01 = v10 = v11 = 0.0f;
-            const int r = ky / 2;
-#pragma unroll 4            // (16 loads in flight per trip group; rolled, each tap row waited for its own four)
-            for (int k = 0; k < ky; ++k) {
-                int ya = y0 + k - r, yb = y1 + k - r;
-                ya = ya < 0 ? -ya : (ya >= d.H ? 2 * d.H - 2 - ya : ya);
-                yb = yb < 0 ? -yb : (yb >= d.H ? 2 * d.H - 2 - yb : yb);
-                const float g = gy[k];
-                v00 += g * p[(size_t)ya * d.W + x0]; v01 += g * p[(size_t)ya * d.W + x1];
-                v10 += g * p[(size_t)yb * d.W + x0]; v11 += g * p[(size_t)yb * d.W + x1];
+            for (int c = 0; c < 3; ++c) {
+                if (c == 0 || planes == 3) {
+                    const float* q = p + c * t.rows * t.cols;
+                    float a0 = q[0], a1 = q[1];
+                    a1 = dx ? a1 : a0;
+                    float v00, v01, v10, v11;
+                    if (!blur) {
+                        q += t.cols;
+                        const float n0 = q[0], n1 = q[1];
+                        v00 = a0; v01 = a1;
+                        v10 = dy ? n0 : a0; v11 = dy ? (dx ? n1 : n0) : a1;
+                    } else {
+                        v00 = v01 = v10 = v11 = 0.0f;
+#pragma unroll 4
+                        for (int k = 0; k < ky; ++k) {
+                            const float g = gy[k];
+                            q += t.cols;
+                            float n0 = q[0], n1 = q[1];
+                            n1 = dx ? n1 : n0;
+                            v00 = fmaf(g, a0, v00); v01 = fmaf(g, a1, v01);
+                            v10 = fmaf(g, dy ? n0 : a0, v10); v11 = fmaf(g, dy ? n1 : a1, v11);
+                            a0 = n0; a1 = n1;
+                        }
+                    }
+                    const float top = fmaf(lx, v01, __fmul_rn(hx, v00)), bot = fmaf(hx, v10, __fmul_rn(lx, v11));
+                    out = __fadd_rn(__fmul_rn(hy, top), __fmul_rn(ly, bot));
+                }
+                img[((size_t)c * d.Hp + yp) * d.Wp + xp] = out;
             }
         }
-        img[((size_t)c * d.Hp + yp) * d.Wp + xp] = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
     }
 }
 
@@ -1172,71 +1273,115 @@ __device__ __forceinline__ float2 feat_pair32(const Pyr& P, const float* __restr
 //  4. score head tail: 3x3 (8->4) SELU, 3x3 (4->4) SELU, 3x3 (4->1), sigmoid.
 //     One kernel, intermediate layers kept in LDS; zero padding at the padded-map border.
 // ------------------------------------------------------------------------ //
-__global__ __launch_bounds__(256) void al_score_tail_kernel(const float* __restrict__ s8, int Hp, int Wp,
-                                                            const float* __restrict__ w2 /*[8][9][4]*/,
-                                                            const float* __restrict__ w4 /*[4][9][4]*/,
-                                                            const float* __restrict__ w6 /*[4][9][1]*/,
-                                                            float* __restrict__ score, int h, int w, int pl,
-                                                            int pt, size_t fs) {
+// r31: register-blocked rows.  In the two 4-channel layers a thread produces a horizontal run of two pixels: per input channel it
+// reads the 3 x 4 window once - a run starts at an even column of rows an even number of floats long, so a window row is two
+// 8-byte reads - and every value feeds up to two taps of the run (the one-pixel form issued a ds_read_b32 per tap for four FMAs,
+// and its staging and layer loops ran a division chain per element).  Per pixel the sum is what it was: channels outermost, taps
+// 0..8, a = fma(v, w, a).  Runs of two keep all four waves at work - 18 runs x 12 rows, then 17 x 10, of 256 threads - and a
+// thread's chain of FMAs as long as the one-pixel form's two passes were; runs of four on 128 threads were measured at
+// 237 us per 8-frame call against the one-pixel form's 127: workgroups in flight are bounded by LDS, so what counts is how long
+// one takes.  The last layer's image takes the first's place in LDS (23.9 KB instead of 29.4: six workgroups per CU).
+constexpr int ST_T = 256;
+constexpr int ST_P0 = ST_W + 6, ST_R0 = ST_H + 6, ST_N0 = 8 * ST_R0 * ST_P0;       // s8 tile: row length, rows, floats
+constexpr int ST_P1 = ST_W + 4, ST_R1 = ST_H + 4, ST_N1 = 4 * ST_R1 * ST_P1;       // first layer's output
+constexpr int ST_P2 = ST_W + 2, ST_R2 = ST_H + 2, ST_N2 = 4 * ST_R2 * ST_P2;       // second layer's
+static_assert(ST_P0 % 2 == 0 && ST_P1 % 2 == 0 && ST_P2 % 2 == 0 && ST_N0 % 2 == 0 && ST_N2 <= ST_N0, "8-byte window reads; t2 in t0's place");
+static_assert(ST_R1 * (ST_P1 / 2) <= ST_T && ST_R2 * (ST_P2 / 2) <= ST_T && ST_H * ST_W == ST_T, "one run per thread and layer");
+static_assert(ST_P0 <= 64 && (8 * ST_R0) % (ST_T / 64) == 0, "staging: a lane per column, the waves take the same number of rows");
+
+// 3 x 3 convolution, CIN -> 4 channels, of the two pixels whose window starts at `tin` (rows P floats, channels `plane` floats apart).
+// One input channel per (rolled) iteration: its 36 wave-uniform weights fit the SGPR file.  Fully unrolled, the 288 scalar
+// weights of the first layer overflow it and come back through ~1000 v_readlane per thread - more than the kernel's FMAs.
+template <int CIN, int P>
+__device__ __forceinline__ void st_conv_run(const float* tin, int plane, const float* __restrict__ w /*[CIN][9][4]*/, float (&a)[2][4]) {
+#pragma unroll 1
+    for (int ci = 0; ci < CIN; ++ci) {
+        float win[3][4];
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) {
+            const float2 q = *reinterpret_cast<const float2*>(tin + dy * P), e = *reinterpret_cast<const float2*>(tin + dy * P + 2);
+            win[dy][0] = q.x; win[dy][1] = q.y; win[dy][2] = e.x; win[dy][3] = e.y;
+        }
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const float v = win[tap / 3][p + tap % 3];
+#pragma unroll
+                for (int o = 0; o < 4; ++o) a[p][o] = fmaf(v, w[(ci * 9 + tap) * 4 + o], a[p][o]);
+            }
+        tin += plane;
+    }
+}
+
+__global__ __launch_bounds__(ST_T) void al_score_tail_kernel(const float* __restrict__ s8, int Hp, int Wp,
+                                                             const float* __restrict__ w2 /*[8][9][4]*/,
+                                                             const float* __restrict__ w4 /*[4][9][4]*/,
+                                                             const float* __restrict__ w6 /*[4][9][1]*/,
+                                                             float* __restrict__ score, int h, int w, int pl,
+                                                             int pt, size_t fs) {
     const Tile3 tb = xcd_band();
     s8 = fsh(s8, tb.z, fs); score = fsh(score, tb.z, fs);
-    __shared__ float t0[8][ST_H + 6][ST_W + 6];
-    __shared__ float t1[4][ST_H + 4][ST_W + 4];
-    __shared__ float t2[4][ST_H + 2][ST_W + 2];
+    __shared__ __attribute__((aligned(16))) float lds[ST_N0 + ST_N1];
+    float* const t0 = lds;                  // [8][ST_R0][ST_P0]
+    float* const t1 = lds + ST_N0;          // [4][ST_R1][ST_P1]
+    float* const t2 = lds;                  // [4][ST_R2][ST_P2], once the first layer has read t0
     const int x0 = tb.x * ST_W, y0 = tb.y * ST_H;
+    const int tid = threadIdx.x;
     const size_t HW = (size_t)Hp * Wp;
-    for (int i = threadIdx.x; i < 8 * (ST_H + 6) * (ST_W + 6); i += 256) {
-        const int c = i / ((ST_H + 6) * (ST_W + 6)), rem = i % ((ST_H + 6) * (ST_W + 6));
-        const int yy = y0 + rem / (ST_W + 6) - 3, xx = x0 + rem % (ST_W + 6) - 3;
-        (&t0[0][0][0])[i] = (yy >= 0 && yy < Hp && xx >= 0 && xx < Wp) ? s8[c * HW + (size_t)yy * Wp + xx] : 0.0f;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < (ST_H + 4) * (ST_W + 4); i += 256) {
-        const int ly = i / (ST_W + 4), lx = i % (ST_W + 4);
-        const int yy = y0 + ly - 2, xx = x0 + lx - 2;
-        float a[4] = {0, 0, 0, 0};
-        if (yy >= 0 && yy < Hp && xx >= 0 && xx < Wp) {
-            // one input channel per (rolled) iteration: its 36 wave-uniform weights fit the SGPR file.
-            // Fully unrolled, the 288 scalar weights overflow it and come back through ~1000
-            // v_readlane per thread - more than the kernel's FMAs.
-#pragma unroll 1
-            for (int ci = 0; ci < 8; ++ci)
+    // staging: a wave per row of t0, a lane per column.  The row's channel, map row and address are wave-uniform (scalar
+    // arithmetic), the lane adds its clamped column: a load, a select and an LDS write per row, and every load in flight at once.
+    // (Dealt 256 elements apart, with channel / row / column stepped per element, the staging was half the kernel's instructions.)
+    if ((tid & 63) < ST_P0) {
+        const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+        const int xx = x0 + lane - 3;
+        const bool xin = xx >= 0 && xx < Wp;
+        const unsigned xb = 4u * (unsigned)min(max(xx, 0), Wp - 1);
 #pragma unroll
-                for (int tap = 0; tap < 9; ++tap) {
-                    const float v = t0[ci][ly + tap / 3][lx + tap % 3];
-#pragma unroll
-                    for (int o = 0; o < 4; ++o) a[o] = fmaf(v, w2[(ci * 9 + tap) * 4 + o], a[o]);
-                }
-            for (int o = 0; o < 4; ++o) a[o] = selu(a[o]);
+        for (int r = 0; r < 8 * ST_R0 / (ST_T / 64); ++r) {
+            const int row = (ST_T / 64) * r + wv, c = row / ST_R0, yy = y0 + row - c * ST_R0 - 3;
+            const float* rowp = s8 + c * HW + (size_t)min(max(yy, 0), Hp - 1) * Wp;
+            const float v = at_b(rowp, xb);
+            t0[row * ST_P0 + lane] = (xin && yy >= 0 && yy < Hp) ? v : 0.0f;
         }
-        for (int o = 0; o < 4; ++o) t1[o][ly][lx] = a[o];
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < (ST_H + 2) * (ST_W + 2); i += 256) {
-        const int ly = i / (ST_W + 2), lx = i % (ST_W + 2);
-        const int yy = y0 + ly - 1, xx = x0 + lx - 1;
-        float a[4] = {0, 0, 0, 0};
-        if (yy >= 0 && yy < Hp && xx >= 0 && xx < Wp) {
-#pragma unroll 1
-            for (int ci = 0; ci < 4; ++ci)
+    {
+        constexpr int RUNS = ST_P1 / 2;
+        const int ly = tid / RUNS, lx = (tid - ly * RUNS) * 2;
+        if (tid < ST_R1 * RUNS) {
+            float a[2][4] = {};
+            st_conv_run<8, ST_P0>(t0 + ly * ST_P0 + lx, ST_R0 * ST_P0, w2, a);
+            const int yy = y0 + ly - 2, xx = x0 + lx - 2;
+            const bool yin = yy >= 0 && yy < Hp, in0 = yin && xx >= 0 && xx < Wp, in1 = yin && xx + 1 >= 0 && xx + 1 < Wp;
 #pragma unroll
-                for (int tap = 0; tap < 9; ++tap) {
-                    const float v = t1[ci][ly + tap / 3][lx + tap % 3];
-#pragma unroll
-                    for (int o = 0; o < 4; ++o) a[o] = fmaf(v, w4[(ci * 9 + tap) * 4 + o], a[o]);
-                }
-            for (int o = 0; o < 4; ++o) a[o] = selu(a[o]);
+            for (int o = 0; o < 4; ++o)             // (zero outside the padded map: the next layer's zero padding)
+                *reinterpret_cast<float2*>(t1 + (o * ST_R1 + ly) * ST_P1 + lx) =
+                    make_float2(in0 ? selu(a[0][o]) : 0.0f, in1 ? selu(a[1][o]) : 0.0f);
         }
-        for (int o = 0; o < 4; ++o) t2[o][ly][lx] = a[o];
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < ST_H * ST_W; i += 256) {        // (ST_H = 8: one pixel per thread)
-        const int lx = i & (ST_W - 1), ly = i / ST_W;
-        const int yy = y0 + ly, xx = x0 + lx;
+    {
+        constexpr int RUNS = ST_P2 / 2;
+        const int ly = tid / RUNS, lx = (tid - ly * RUNS) * 2;
+        if (tid < ST_R2 * RUNS) {
+            float a[2][4] = {};
+            st_conv_run<4, ST_P1>(t1 + ly * ST_P1 + lx, ST_R1 * ST_P1, w4, a);
+            const int yy = y0 + ly - 1, xx = x0 + lx - 1;
+            const bool yin = yy >= 0 && yy < Hp, in0 = yin && xx >= 0 && xx < Wp, in1 = yin && xx + 1 >= 0 && xx + 1 < Wp;
+#pragma unroll
+            for (int o = 0; o < 4; ++o)
+                *reinterpret_cast<float2*>(t2 + (o * ST_R2 + ly) * ST_P2 + lx) =
+                    make_float2(in0 ? selu(a[0][o]) : 0.0f, in1 ? selu(a[1][o]) : 0.0f);
+        }
+    }
+    __syncthreads();
+    {                                               // the one-channel layer: a pixel per thread
+        const int lx = tid & (ST_W - 1), ly = tid / ST_W;
         float a = 0.0f;
         for (int ci = 0; ci < 4; ++ci)
-            for (int tap = 0; tap < 9; ++tap) a = fmaf(t2[ci][ly + tap / 3][lx + tap % 3], w6[ci * 9 + tap], a);
-        const int uy = yy - pt, ux = xx - pl;
+            for (int tap = 0; tap < 9; ++tap) a = fmaf(t2[(ci * ST_R2 + ly + tap / 3) * ST_P2 + lx + tap % 3], w6[ci * 9 + tap], a);
+        const int uy = y0 + ly - pt, ux = x0 + lx - pl;
         if (uy >= 0 && uy < h && ux >= 0 && ux < w) score[(size_t)uy * w + ux] = 1.0f / (1.0f + expf(-a));
     }
 }
@@ -1984,7 +2129,7 @@ struct sslam_aliked {
     // workspace
     ALCtrl* ctrl;
     uint8_t* in_u8;
-    float *fsrc, *img, *x1, *x2, *p3, *off, *t3, *x3, *p4, *t4, *x4, *g2, *g3, *g4;
+    float *img, *x1, *x2, *p3, *off, *t3, *x3, *p4, *t4, *x4, *g2, *g3, *g4;
     float *s8, *rnorm, *score, *nms, *bsum, *gk, *g1cl, *g2cl, *g3cl, *g4cl, *pre2, *pre3, *pre4;
     unsigned long long* cand;
     unsigned* hist;
@@ -2047,8 +2192,8 @@ int al_enqueue(sslam_aliked* g, const sslam::ALPlan& p, const FrameIn& srcs, int
     const dim3 b256(256);
     hipLaunchKernelGGL(al_reset_kernel, dim3(F), b256, 0, s, g->ctrl, g->hist, fs, g->gk, p.kx, p.sx, p.ky, p.sy);
 
-    hipLaunchKernelGGL(al_to_float_kernel, dim3(p.to_float_gx, d.H, F), b256, 0, s, srcs, g->fsrc, d, g->gk, p.kx, p.blur, fs);
-    hipLaunchKernelGGL(al_resize_pad_kernel, dim3(p.pad_gx, d.Hp, F), b256, 0, s, g->fsrc, g->img, d, g->gk + 32, p.ky, p.blur, fs);
+    hipLaunchKernelGGL(al_preprocess_kernel, dim3(p.pre_gx, p.pre_gy, F), b256, (size_t)p.pre_lds, s, srcs, g->img, d, g->gk, p.kx, p.ky,
+                       p.blur, PreTile{p.pre_tw, p.pre_th, p.pre_cols, p.pre_rows, p.pre_raw}, fs);
     // block1 (conv1 + conv2 fused), block2 at 1/2 (pooling + conv1 + 1 x 1 branch + conv2 + residual fused)
     hipLaunchKernelGGL(al_block1_rows_kernel, dim3(p.b1_strips, p.b1_nb, F), dim3(64), 0, s, g->img, g->x1, d.Hp, d.Wp, p.b1_hs,
                        g->b1c1.w, g->b1c1.a, g->b1c1.b, g->b1c2f, g->b1c2.a, g->b1c2.b, g->ctrl, fs);
@@ -2081,7 +2226,7 @@ int al_enqueue(sslam_aliked* g, const sslam::ALPlan& p, const FrameIn& srcs, int
     hipLaunchKernelGGL(al_agg_pre_kernel, dim3(p.agg_pre_gx, F), b256, 0, s, g->g2, g->g3, g->g4, g->sh0, g->pre2, g->pre3, g->pre4,
                        d.Hp, d.Wp, fs);
     hipLaunchKernelGGL(al_aggregate_kernel, dim3(p.pad_gx, d.Hp, F), b256, 0, s, P, g->sh0, g->s8, g->rnorm, fs);
-    hipLaunchKernelGGL(al_score_tail_kernel, dim3(p.tail_gx, p.tail_gy, F), b256, 0, s, g->s8, d.Hp, d.Wp, g->sh2, g->sh4, g->sh6,
+    hipLaunchKernelGGL(al_score_tail_kernel, dim3(p.tail_gx, p.tail_gy, F), dim3(ST_T), 0, s, g->s8, d.Hp, d.Wp, g->sh2, g->sh4, g->sh6,
                        g->score, d.h, d.w, d.pl, d.pt, fs);
     // DKD
     hipLaunchKernelGGL(al_nms_wave_kernel, dim3(p.nms_gx, F), b256, 0, s, g->score, d.h, d.w, p.nbx, p.n_tiles, g->nms, g->bsum, 0.2f,
@@ -2172,7 +2317,7 @@ int sslam_aliked_create_batched(sslam_ctx* ctx, const float* weights, size_t n_f
     auto bind_frame = [&](sslam::Slab& A) {
         g->ctrl = A.take<ALCtrl>(e.ctrl);
         g->in_u8 = A.take<uint8_t>(e.in_u8);
-        g->fsrc = A.take<float>(e.fsrc); g->img = A.take<float>(e.img);
+        g->img = A.take<float>(e.img);       // (e.fsrc, the float image between the two pre-processing launches of old, is no longer carved)
         g->x1 = A.take<float>(e.x1); g->x2 = A.take<float>(e.x2);
         g->p3 = A.take<float>(e.p3); g->off = A.take<float>(e.off);
         g->t3 = A.take<float>(e.t3); g->x3 = A.take<float>(e.x3);
