@@ -224,6 +224,41 @@ int sslam_triangulate_2view_dev(sslam_ctx* ctx, int n_max, const int32_t* n_dev,
                                 double reproj_px_max, double* X_out_dev, int32_t* ij_out_dev,
                                 int32_t* info_out_dev, int32_t* reason_out_dev, double* diag_out_dev);
 
+/* ------------------------------------------------ multi-view triangulation
+ * The numeric body of `multi_view_triangulation` / `MultiViewTriangulator` (slam/core/multi_view_utils.py, the
+ * module the reference's tests call and its tree no longer holds; PARITY UNPINNED), for n_tracks tracks in one
+ * call.  Observations are CSR: track i owns observations track_off[i] .. track_off[i+1]-1, observation o is the
+ * pixel obs_uv[o] (float32, used as doubles) in view obs_view[o] of the n_views views Tcw[n_views][16]
+ * (row-major camera-from-world).  Per view P = K Tcw[:3]; per track the rows u P[2] - P[0], v P[2] - P[1] of its
+ * observations stack to A [2V, 4], Xh is the unit right singular vector of A's smallest singular value (A is
+ * reduced to its 4 x 4 triangular factor by Givens rotations, then the one-sided Jacobi SVD of the two-view
+ * entry; no cap on V), X = Xh[:3] / w, z_k = (Tcw_k X)[2].  Every track gets one reason, decided in this order:
+ *   1 too_few_views (V < 2), 2 invalid_w (w not finite or |w| <= 1e-12), 3 bad_depth (some z_k outside
+ *   [min_depth, max_depth]), 4 behind_cam (some z_k <= 1e-6), 5 high_reproj (the MEAN over the track's views of
+ *   the pixel error ||K (Tcw_k X) / z_k - (u_k, v_k)|| exceeds max_rep_err), else 0 kept.  fp64 throughout.
+ *   X_out[n_tracks*3] : the kept points, compacted in track order;  idx_out[n_tracks] : their track indices
+ *   info_out[8] : kept, then the counts of reasons 0 .. 5, then n_tracks;  n_tracks == 0 is legal
+ *   reason_out[n_tracks] (may be NULL) : the reason per track;  diag_out[n_tracks*3] (may be NULL) : mean pixel
+ *   error, smallest and largest z_k per track (NaN where there is no point; +inf error behind a camera)
+ * An offset array that decreases or a view index outside [0, n_views) is an error. */
+int sslam_triangulate_tracks_host(sslam_ctx* ctx, int n_tracks, int n_views, const int32_t* track_off,
+                                  const int32_t* obs_view, const float* obs_uv, const double* K9,
+                                  const double* Tcw, double min_depth, double max_depth, double max_rep_err,
+                                  double* X_out, int32_t* idx_out, int32_t* info_out, int32_t* reason_out,
+                                  double* diag_out);
+
+/* ------------------------------------------------ landmark pairs within a radius
+ * Every (i, j), i < j, of pos[n][3] (double) with dx^2 + dy^2 + dz^2 <= radius^2 in fp64 - what
+ * `cKDTree(pos).query_pairs(radius)` returns, the input of `Map.fuse_closeby_duplicate_landmarks`
+ * (slam/core/landmark_utils.py:138-161).  A non-finite coordinate pairs with nothing.
+ *   pairs_out[cap][2] (host) : the first min(*count_out, cap) pairs found, in NO particular order (sort them)
+ *   count_out : the exact number of pairs, also when it exceeds cap - call again with a buffer of that size
+ * `_host` takes the positions from host memory, `_dev` from device memory (the Map's device mirror). */
+int sslam_close_pairs_host(sslam_ctx* ctx, int n, const double* pos, double radius, int64_t cap,
+                           int32_t* pairs_out, int64_t* count_out);
+int sslam_close_pairs_dev(sslam_ctx* ctx, int n, const double* pos_dev, double radius, int64_t cap,
+                          int32_t* pairs_out, int64_t* count_out);
+
 /* ------------------------------------------------ two-view relative pose
  * Replaces `cv2.recoverPose(E, pts_ref, pts_cur, K)` in `recover_pose_from_fundamental`
  * (slam/core/two_view_bootstrap.py:207-208) and in the tracking-lost fallback (slam/monocular/main_revamped.py:514):

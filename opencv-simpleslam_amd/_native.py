@@ -65,6 +65,10 @@ def _signatures():
                                                vp, vp, vp, vp, vp]),
         "sslam_triangulate_2view_dev": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, i32, C.c_double,
                                               C.c_double, vp, vp, vp, vp, vp]),
+        "sslam_triangulate_tracks_host": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double,
+                                                vp, vp, vp, vp, vp]),
+        "sslam_close_pairs_host": (i32, [vp, i32, vp, C.c_double, C.c_int64, vp, vp]),
+        "sslam_close_pairs_dev": (i32, [vp, i32, vp, C.c_double, C.c_int64, vp, vp]),
         "sslam_recover_pose_host": (i32, [vp, i32, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp]),
         "sslam_two_view_metrics_host": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "sslam_homography_ransac_host": (i32, [vp, i32, vp, vp, C.c_double, C.c_double, i32, vp, vp, vp]),

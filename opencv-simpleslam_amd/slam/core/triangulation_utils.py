@@ -23,6 +23,7 @@ import logging
 import numpy as np
 
 from .features_utils import feature_matcher, filter_matches_ransac
+from .multi_view_utils import multi_view_triangulation        # noqa: F401  (the reference's tests import it from here too)
 from .two_view_bootstrap import pts_from_matches
 from ... import triangulation as _tri
 
