@@ -20,11 +20,10 @@ frame with more candidates than `max_candidates` or more keypoints than `max_key
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _native
+from ._detector import CapacityDetector
 
 # cv2's values
 DESCRIPTOR_KAZE_UPRIGHT, DESCRIPTOR_KAZE, DESCRIPTOR_MLDB_UPRIGHT, DESCRIPTOR_MLDB = 2, 3, 4, 5
@@ -37,8 +36,10 @@ _INFO = ("w", "h", "levels", "octaves", "octave", "sigma_size", "border", "one_w
          "max_keypoints")
 
 
-class AKAZE:
+class AKAZE(CapacityDetector):
     """`cv2.AKAZE` with `detectAndCompute(image, mask=None)`.  The device instance is made at the first call."""
+    NAME, PREFIX = "AKAZE", "akaze"
+    ROWS = ((2,), np.float32), ((3,), np.float32), ((2,), np.int32), ((DESC_BYTES,), np.uint8)
 
     def __init__(self, descriptor_type=DESCRIPTOR_MLDB, descriptor_size=0, descriptor_channels=3, threshold=0.001, nOctaves=4, nOctaveLayers=4,
                  diffusivity=DIFF_PM_G2, max_points=-1, *, max_h=2160, max_w=4096, max_candidates=0, max_keypoints=0, ctx=None):
@@ -66,70 +67,17 @@ class AKAZE:
         self.descriptor_type, self.descriptor_size, self.descriptor_channels = int(descriptor_type), 0, 3
         self.threshold, self.nOctaves, self.nOctaveLayers = float(threshold), nOctaves, nOctaveLayers
         self.diffusivity, self.max_points = int(diffusivity), max_points
-        self.max_h, self.max_w = int(max_h), int(max_w)
         self.max_candidates, self.max_keypoints = int(max_candidates), int(max_keypoints)
-        self.ctx = ctx
-        self.handle = None
-        self.capacity = 0                  # rows of every output array
-        self.candidate_capacity = 0
-        self._out = None                   # the host entry's output arrays, made once
+        self._setup(max_h, max_w, ctx)
 
-    def _instance(self):
-        if self.handle is None:
-            self.ctx = self.ctx or _native.default_context()
-            h = C.c_void_p()
-            L = _native.lib()
-            _native.check(L.sslam_akaze_create(self.ctx.handle, self.max_w, self.max_h, self.descriptor_type, self.descriptor_size,
-                                               self.descriptor_channels, self.threshold, self.nOctaves, self.nOctaveLayers, self.diffusivity,
-                                               self.max_points, self.max_candidates, self.max_keypoints, C.byref(h)), "sslam_akaze_create")
-            self.handle = h
-            rows, cand = C.c_int(0), C.c_int(0)
-            _native.check(L.sslam_akaze_capacity(h, C.byref(rows), C.byref(cand)), "sslam_akaze_capacity")
-            self.capacity, self.candidate_capacity = int(rows.value), int(cand.value)
-        return self.handle
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _native.lib().sslam_akaze_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _image(self, img, mask):
-        """`img` as the contiguous uint8 [h, w, c] the library takes; anything else is refused, never cast or clipped."""
-        if mask is not None:
-            raise ValueError("AKAZE.detectAndCompute: a mask is not supported")
-        img = np.asarray(img)
-        if img.dtype != np.uint8:
-            raise TypeError(f"AKAZE.detectAndCompute: image is {img.dtype}, want uint8")
-        if img.ndim == 2:
-            img = img[:, :, None]
-        if img.ndim != 3 or img.shape[2] not in (1, 3, 4) or img.shape[0] < 1 or img.shape[1] < 1:
-            raise ValueError(f"AKAZE.detectAndCompute: image must be [h, w] or [h, w, 1 | 3 | 4], got shape {img.shape}")
-        if img.shape[0] > self.max_h or img.shape[1] > self.max_w:
-            raise ValueError(f"AKAZE.detectAndCompute: image {img.shape[1]}x{img.shape[0]} is larger than the instance's "
-                             f"{self.max_w}x{self.max_h} (max_w x max_h)")
-        return np.ascontiguousarray(img)
+    def _create(self, L, handle_ref):
+        return L.sslam_akaze_create(self.ctx.handle, self.max_w, self.max_h, self.descriptor_type, self.descriptor_size,
+                                    self.descriptor_channels, self.threshold, self.nOctaves, self.nOctaveLayers, self.diffusivity,
+                                    self.max_points, self.max_candidates, self.max_keypoints, handle_ref)
 
     def detect_arrays(self, img, mask=None):
         """-> (xy float32 [N,2], aux float32 [N,3] = size, angle, response, lvl int32 [N,2] = octave, class_id, desc uint8 [N,61])."""
-        img = self._image(img, mask)
-        h = self._instance()
-        if self._out is None:
-            cap = self.capacity
-            self._out = (np.empty((cap, 2), np.float32), np.empty((cap, 3), np.float32), np.empty((cap, 2), np.int32),
-                         np.empty((cap, DESC_BYTES), np.uint8))
-        xy, aux, lvl, desc = self._out
-        n = C.c_int32(0)
-        P = _native.ptr
-        _native.check(_native.lib().sslam_akaze_detect_host(h, P(img), img.shape[0], img.shape[1], img.shape[2], P(xy), P(aux), P(lvl), P(desc),
-                                                            C.byref(n)), "sslam_akaze_detect_host")
-        k = n.value
-        return xy[:k].copy(), aux[:k].copy(), lvl[:k].copy(), desc[:k].copy()
+        return self._detect_host(img, mask)
 
     def detectAndCompute(self, image, mask=None):
         """-> (list of KeyPoint with every field set, descriptors uint8 [N, 61]); ([], None) without a keypoint.  KeyPoint is
@@ -141,32 +89,16 @@ class AKAZE:
         kps = [KeyPoint(x, y, s, a, r, o, c) for (x, y), (s, a, r), (o, c) in zip(xy.tolist(), aux.tolist(), lvl.tolist())]
         return kps, desc
 
-    @property
-    def chain_rows(self) -> int:
-        """The row bound to hand `BFMatcher.match_dev` (M, N) and `epipolar.filter_matches_dev` (n_max) for this instance's
-        device outputs: min(capacity, 65 536), the matcher's limit; the arrays themselves hold `capacity` rows."""
-        from .bf_matcher import MAX_ROWS
-        self._instance()
-        return min(self.capacity, MAX_ROWS)
-
     def detect_dev(self, img_dev, h: int, w: int, c: int, xy_out_dev, aux_out_dev, lvl_out_dev, desc_out_dev, n_out_dev):
         """Device-resident call: the `*_dev` arguments are device pointers (ints) - the image uint8 [h, w, c], xy float32
         [capacity, 2], aux float32 [capacity, 3], lvl int32 [capacity, 2], desc uint8 [capacity, 61], the count int32 [1] - and
         everything stays on the device: `desc_out_dev` / `n_out_dev` are what `BFMatcher.match_dev` takes as `q_dev` / `m_dev`
         (NORM_HAMMING, D = 61, `chain_rows` as its M), `xy_out_dev` what `epipolar.filter_matches_dev` takes as `xy1_dev`.
         Enqueued on the instance's context stream, no synchronisation; a voided frame writes the count 0 and sets `overflow()`."""
-        if not (1 <= int(h) <= self.max_h and 1 <= int(w) <= self.max_w):
-            raise ValueError(f"AKAZE.detect_dev: image {w}x{h} is larger than the instance's {self.max_w}x{self.max_h}")
+        self._check_dev_size(h, w)
         P = _native.ptr
         _native.check(_native.lib().sslam_akaze_detect_dev(self._instance(), P(img_dev), int(h), int(w), int(c), P(xy_out_dev), P(aux_out_dev),
                                                            P(lvl_out_dev), P(desc_out_dev), P(n_out_dev)), "sslam_akaze_detect_dev")
-
-    def overflow(self) -> int:
-        """The sticky word: bit 0 - a frame had more candidates than `max_candidates`, bit 1 - more keypoints than
-        `max_keypoints`; such a frame was voided.  Synchronises the stream."""
-        v = C.c_int(0)
-        _native.check(_native.lib().sslam_akaze_overflow(self._instance(), C.byref(v)), "sslam_akaze_overflow")
-        return int(v.value)
 
     # test hooks (include/sslam_hip.h: sslam_akaze_level_info, sslam_akaze_stage_read)
     def level_info(self, level: int):

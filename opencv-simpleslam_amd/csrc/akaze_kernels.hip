@@ -34,6 +34,8 @@
 // capacity is voided (count 0, the sticky overflow word), never truncated.  A descriptor row is written as 61 single bytes.
 // PARITY UNPINNED: cv2 is absent here; tests/akaze_ref.py names what could not be confirmed.
 #include "common.hpp"
+#include "feat_device.hpp"
+#include "feat_host.hpp"
 #include "geom_common.hpp"
 #include "akaze_plan.hpp"
 
@@ -84,15 +86,6 @@ struct AkzArgs {
     AkzLevDev lv[AKZ_MAX_LEVELS];
 };
 
-__device__ __forceinline__ int akz_reflect101(int i, int n) {
-    if ((unsigned)i < (unsigned)n) return i;
-    if (n == 1) return 0;
-    const int p = 2 * (n - 1);
-    i %= p;
-    if (i < 0) i += p;
-    return i < n ? i : p - i;
-}
-
 __device__ __forceinline__ int akz_clamp(int i, int n) { return min(max(i, 0), n - 1); }
 
 // ---- grey, the blurs, the halving -------------------------------------------------------------------------------------------
@@ -100,8 +93,7 @@ __global__ __launch_bounds__(AKZ_T) void akz_grey_kernel(const uint8_t* __restri
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * AKZ_WAVES + (threadIdx.x >> 6);
     if (x >= w || y >= h) return;
     const uint8_t* s = src + ((size_t)y * w + x) * C;
-    const int g = C == 1 ? (int)s[0] : ((int)s[0] * 3735 + (int)s[1] * 19235 + (int)s[2] * 9798 + (1 << 14)) >> 15;
-    dst[(size_t)y * w + x] = (float)g / 255.f;
+    dst[(size_t)y * w + x] = (float)bgr_to_grey(s, C) / 255.f;
 }
 
 // acc = 0; for k ascending: acc = acc + tap_k * px_k, the product and the sum each rounded; BORDER_REPLICATE
@@ -148,10 +140,10 @@ __global__ __launch_bounds__(AKZ_T) void akz_halve_kernel(const float* __restric
 // ---- the separable Scharr form at reach s with smoothing taps (a, b, a), BORDER_REFLECT_101 ---------------------------------------
 // x: the row pass differentiates (p[+s] - p[-s]), the column pass smooths; y: the row pass smooths, the column pass differentiates
 __device__ __forceinline__ float akz_dx(const float* p, int w, int h, int x, int y, int s, float a, float b) {
-    const int xm = akz_reflect101(x - s, w), xp = akz_reflect101(x + s, w);
-    const float* r0 = p + (size_t)akz_reflect101(y - s, h) * w;
+    const int xm = reflect101(x - s, w), xp = reflect101(x + s, w);
+    const float* r0 = p + (size_t)reflect101(y - s, h) * w;
     const float* r1 = p + (size_t)y * w;
-    const float* r2 = p + (size_t)akz_reflect101(y + s, h) * w;
+    const float* r2 = p + (size_t)reflect101(y + s, h) * w;
     const float d0 = r0[xp] - r0[xm], d1 = r1[xp] - r1[xm], d2 = r2[xp] - r2[xm];
     float acc = a * d0;
     float t = b * d1; acc = acc + t;
@@ -167,9 +159,9 @@ __device__ __forceinline__ float akz_smooth_row(const float* r, int xm, int x, i
 }
 
 __device__ __forceinline__ float akz_dy(const float* p, int w, int h, int x, int y, int s, float a, float b) {
-    const int xm = akz_reflect101(x - s, w), xp = akz_reflect101(x + s, w);
-    const float s0 = akz_smooth_row(p + (size_t)akz_reflect101(y - s, h) * w, xm, x, xp, a, b);
-    const float s1 = akz_smooth_row(p + (size_t)akz_reflect101(y + s, h) * w, xm, x, xp, a, b);
+    const int xm = reflect101(x - s, w), xp = reflect101(x + s, w);
+    const float s0 = akz_smooth_row(p + (size_t)reflect101(y - s, h) * w, xm, x, xp, a, b);
+    const float s1 = akz_smooth_row(p + (size_t)reflect101(y + s, h) * w, xm, x, xp, a, b);
     return s1 - s0;
 }
 
@@ -440,23 +432,15 @@ __global__ __launch_bounds__(AKZ_T) __attribute__((target("no-packed-fp32-ops"))
     }
 }
 
-__device__ __forceinline__ int akz_wave_sum(int v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ bool akz_void(const AkzArgs& a) { return a.ctl->ncand > a.cand_cap || a.ctl->nkp > a.kp_cap; }
-
 __global__ __launch_bounds__(AKZ_T) void akz_quota_kernel(AkzArgs a) {
-    if (akz_void(a)) return;
+    if (feat_voided(a)) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = a.ctl->nkp;
     for (int j = blockIdx.x * AKZ_WAVES + wave; j < n; j += gridDim.x * AKZ_WAVES) {
         int above = 0;
         if (a.max_points > 0) {
             const float mine = __uint_as_float(a.kp[8 * (size_t)j + 4]);
             for (int i = lane; i < n; i += 64) above += __uint_as_float(a.kp[8 * (size_t)i + 4]) > mine;
-            above = akz_wave_sum(above);
+            above = wave_sum(above);
         }
         const bool kept = a.max_points <= 0 || above < a.max_points;
         if (lane == 0) {
@@ -467,33 +451,12 @@ __global__ __launch_bounds__(AKZ_T) void akz_quota_kernel(AkzArgs a) {
 }
 
 // ---- the main orientation: a kept keypoint per wavefront -------------------------------------------------------------------------
-__device__ __forceinline__ float akz_atan2(const AkzConsts& k, float fy, float fx) {
-    const float ax = fabsf(fx), ay = fabsf(fy);
-    float ang;
-    if (ax >= ay) {
-        const float q = ay / (ax + k.atan_eps), q2 = q * q;
-        float t = k.atan_p7 * q2; t = t + k.atan_p5; t = t * q2; t = t + k.atan_p3; t = t * q2; t = t + k.atan_p1;
-        ang = t * q;
-    } else {
-        const float q = ax / (ay + k.atan_eps), q2 = q * q;
-        float t = k.atan_p7 * q2; t = t + k.atan_p5; t = t * q2; t = t + k.atan_p3; t = t * q2; t = t + k.atan_p1;
-        t = t * q;
-        ang = 90.f - t;
-    }
-    if (fx < 0.f) ang = 180.f - ang;
-    if (fy < 0.f) ang = 360.f - ang;
-    return ang;
-}
-
-__device__ __forceinline__ long long akz_fixed(float v) { return (long long)((double)v * (double)(1ull << AKZ_FIXED_LOG2)); }
-__device__ __forceinline__ float akz_unfixed(long long s) { return (float)((double)s / (double)(1ull << AKZ_FIXED_LOG2)); }
-
 struct AkzGauss { float g[7][7]; };
 
 __global__ __launch_bounds__(AKZ_T) __attribute__((target("no-packed-fp32-ops"))) void akz_orient_kernel(AkzArgs a, AkzGauss G) {
     __shared__ long long s_fx[AKZ_WAVES][AKZ_ORI_GRID], s_fy[AKZ_WAVES][AKZ_ORI_GRID];
     __shared__ float s_ang[AKZ_WAVES][AKZ_ORI_GRID];
-    if (akz_void(a)) return;
+    if (feat_voided(a)) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = a.ctl->nkp;
     const AkzConsts& K = a.k;
     for (int j = blockIdx.x * AKZ_WAVES + wave; j < n; j += gridDim.x * AKZ_WAVES) {
@@ -513,8 +476,8 @@ __global__ __launch_bounds__(AKZ_T) __attribute__((target("no-packed-fp32-ops"))
                 if (iy >= 0 && iy < L.h && ix >= 0 && ix < L.w) {
                     const float gw = G.g[abs(i)][abs(jj)];
                     const float rx = gw * LX[(size_t)iy * L.w + ix], ry = gw * LY[(size_t)iy * L.w + ix];
-                    ang = akz_atan2(K, ry, rx) * K.deg2rad;
-                    fx = akz_fixed(rx); fy = akz_fixed(ry);
+                    ang = fast_atan2_deg(K.atan, ry, rx) * K.atan.deg2rad;
+                    fx = to_fixed<AKZ_FIXED_LOG2>(rx); fy = to_fixed<AKZ_FIXED_LOG2>(ry);
                 }
             }
             s_fx[wave][e] = fx; s_fy[wave][e] = fy; s_ang[wave][e] = ang;
@@ -532,7 +495,7 @@ __global__ __launch_bounds__(AKZ_T) __attribute__((target("no-packed-fp32-ops"))
                 const bool in = a1 < a2 ? (a1 < ang && ang < a2) : ((ang > 0.f && ang < a2) || (ang > a1 && ang < K.two_pi));
                 if (in) { sx += s_fx[wave][e]; sy += s_fy[wave][e]; }
             }
-            sxf = akz_unfixed(sx); syf = akz_unfixed(sy);
+            sxf = from_fixed<AKZ_FIXED_LOG2>(sx); syf = from_fixed<AKZ_FIXED_LOG2>(sy);
             const float xx = sxf * sxf, yy = syf * syf;
             best = xx + yy;
         }
@@ -545,7 +508,7 @@ __global__ __launch_bounds__(AKZ_T) __attribute__((target("no-packed-fp32-ops"))
             const int ow = __shfl_xor(bw, o);
             if (ov > bv || (ov == bv && ow < bw)) { bv = ov; bw = ow; }
         }
-        const float angle = akz_atan2(K, syf, sxf);
+        const float angle = fast_atan2_deg(K.atan, syf, sxf);
         const float win = __shfl(angle, bw);
         if (lane == 0) rec[3] = __float_as_uint(bv > 0.f ? win : 0.f);
         __builtin_amdgcn_wave_barrier();
@@ -559,7 +522,7 @@ __global__ __launch_bounds__(AKZ_T) __attribute__((target("no-packed-fp32-ops"))
     __shared__ float s_val[AKZ_WAVES][AKZ_CELLS][3];
     __shared__ uint32_t s_bits[AKZ_WAVES][16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool voided = akz_void(a);
+    const bool voided = feat_voided(a);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         a.n_out[0] = voided ? 0 : a.ctl->nout;
         if (voided) atomicOr(a.sticky, (a.ctl->ncand > a.cand_cap ? 1 : 0) | (a.ctl->nkp > a.kp_cap ? 2 : 0));
@@ -572,13 +535,13 @@ __global__ __launch_bounds__(AKZ_T) __attribute__((target("no-packed-fp32-ops"))
         const unsigned long long key = a.kkey[j];
         int less = 0;
         for (int i = lane; i < n; i += 64) less += a.kflag[i] && a.kkey[i] < key;
-        const int pos = akz_wave_sum(less);
+        const int pos = wave_sum(less);
         const uint32_t* rec = a.kp + 8 * (size_t)j;
         const AkzLevDev L = a.lv[rec[6]];
         const float x = __uint_as_float(rec[0]), y = __uint_as_float(rec[1]), size = __uint_as_float(rec[2]), angle = __uint_as_float(rec[3]);
         const float xf = x / L.ratio, yf = y / L.ratio;
         const float scale = (float)(int)rintf((0.5f * size) / L.ratio);
-        const float rad = angle * K.deg2rad;
+        const float rad = angle * K.atan.deg2rad;
         const float co = (float)cos((double)rad), si = (float)sin((double)rad);
         const float* LT = a.Lt + L.off;
         const float* LX = a.Lx + L.off;
@@ -603,9 +566,9 @@ __global__ __launch_bounds__(AKZ_T) __attribute__((target("no-packed-fp32-ops"))
                 const float t0 = rx * co, t1 = ry * si, t2 = (-rx) * si, t3 = ry * co;
                 const float rry = t0 + t1, rrx = t2 + t3;
                 const int cell = cell0 + (kk / step) * cells + ll / step;          // < AKZ_CELLS: kk, ll < cells * step
-                atomicAdd(&s_acc[wave][cell][0], (unsigned long long)akz_fixed(ri));
-                atomicAdd(&s_acc[wave][cell][1], (unsigned long long)akz_fixed(rrx));
-                atomicAdd(&s_acc[wave][cell][2], (unsigned long long)akz_fixed(rry));
+                atomicAdd(&s_acc[wave][cell][0], (unsigned long long)to_fixed<AKZ_FIXED_LOG2>(ri));
+                atomicAdd(&s_acc[wave][cell][1], (unsigned long long)to_fixed<AKZ_FIXED_LOG2>(rrx));
+                atomicAdd(&s_acc[wave][cell][2], (unsigned long long)to_fixed<AKZ_FIXED_LOG2>(rry));
                 atomicAdd(&s_cnt[wave][cell], 1);
             }
             cell0 += cells * cells;
@@ -615,7 +578,7 @@ __global__ __launch_bounds__(AKZ_T) __attribute__((target("no-packed-fp32-ops"))
         if (lane < AKZ_CELLS) {
             const int cnt = s_cnt[wave][lane];
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) s_val[wave][lane][ch] = cnt > 0 ? akz_unfixed((long long)s_acc[wave][lane][ch]) / (float)cnt : 0.f;
+            for (int ch = 0; ch < 3; ++ch) s_val[wave][lane][ch] = cnt > 0 ? from_fixed<AKZ_FIXED_LOG2>((long long)s_acc[wave][lane][ch]) / (float)cnt : 0.f;
         }
         __builtin_amdgcn_wave_barrier();
         __threadfence_block();
@@ -776,14 +739,6 @@ int akaze_enqueue(sslam_akaze* o, const uint8_t* img_dev, int h, int w, int c, f
     return 0;
 }
 
-int akaze_check_call(const char* who, sslam_akaze* o, const void* img, int h, int w, int c) {
-    SSLAM_REQUIRE(o != nullptr, "%s: instance is NULL", who);
-    SSLAM_REQUIRE(img != nullptr, "%s: img is NULL", who);
-    char msg[160];
-    if (akz_check_image(w, h, c, o->max_w, o->max_h, msg, sizeof msg)) { sslam::set_error("%s: %s", who, msg); return 2; }
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int sslam_akaze_create(sslam_ctx* ctx, int max_w, int max_h, int descriptor_type, int descriptor_size, int descriptor_channels,
@@ -825,28 +780,17 @@ extern "C" int sslam_akaze_destroy(sslam_akaze* o) {
 }
 
 extern "C" int sslam_akaze_capacity(sslam_akaze* o, int* rows, int* candidates) {
-    const char* who = "sslam_akaze_capacity";
-    SSLAM_REQUIRE(o != nullptr && rows != nullptr, "%s: NULL argument", who);
-    *rows = o->kp_cap;
-    if (candidates) *candidates = o->cand_cap;
-    return 0;
+    return sslam::feat_capacity("sslam_akaze_capacity", o, rows, candidates);
 }
 
 extern "C" int sslam_akaze_overflow(sslam_akaze* o, int* word) {
-    const char* who = "sslam_akaze_overflow";
-    SSLAM_REQUIRE(o != nullptr && word != nullptr, "%s: NULL argument", who);
-    SSLAM_HIP_CHECK(hipSetDevice(o->ctx->device));
-    int32_t v = 0;
-    SSLAM_HIP_CHECK(sslam::copy_down(o->ctx->stream, &v, o->sticky, 1));
-    SSLAM_HIP_CHECK(hipStreamSynchronize(o->ctx->stream));
-    *word = v;
-    return 0;
+    return sslam::feat_overflow("sslam_akaze_overflow", o, word);
 }
 
 extern "C" int sslam_akaze_detect_dev(sslam_akaze* o, const uint8_t* img_dev, int h, int w, int c, float* xy_out_dev, float* aux_out_dev,
                                       int32_t* lvl_out_dev, uint8_t* desc_out_dev, int32_t* n_out_dev) {
     const char* who = "sslam_akaze_detect_dev";
-    if (int rc = akaze_check_call(who, o, img_dev, h, w, c)) return rc;
+    if (int rc = feat_check_call(who, o, img_dev, h, w, c)) return rc;
     SSLAM_REQUIRE(xy_out_dev && aux_out_dev && lvl_out_dev && desc_out_dev && n_out_dev, "%s: an output pointer is NULL", who);
     SSLAM_HIP_CHECK(hipSetDevice(o->ctx->device));
     return akaze_enqueue(o, img_dev, h, w, c, xy_out_dev, aux_out_dev, lvl_out_dev, desc_out_dev, n_out_dev);
@@ -855,35 +799,13 @@ extern "C" int sslam_akaze_detect_dev(sslam_akaze* o, const uint8_t* img_dev, in
 extern "C" int sslam_akaze_detect_host(sslam_akaze* o, const uint8_t* img, int h, int w, int c, float* xy_out, float* aux_out, int32_t* lvl_out,
                                        uint8_t* desc_out, int32_t* n_out) {
     const char* who = "sslam_akaze_detect_host";
-    if (int rc = akaze_check_call(who, o, img, h, w, c)) return rc;
+    if (int rc = feat_check_call(who, o, img, h, w, c)) return rc;
     SSLAM_REQUIRE(xy_out && aux_out && lvl_out && desc_out && n_out, "%s: an output pointer is NULL", who);
-    SSLAM_HIP_CHECK(hipSetDevice(o->ctx->device));
-    const size_t bytes = (size_t)h * w * c;
-    char* b;
-    if (int rc = sslam::ctx_scratch(o->ctx, bytes, &b)) return rc;
-    hipStream_t s = o->ctx->stream;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b, img, bytes, hipMemcpyHostToDevice, s));
-    if (int rc = akaze_enqueue(o, (const uint8_t*)b, h, w, c, o->xy, o->aux, o->lvl, o->desc, o->n)) return rc;
-    int32_t n = 0;
-    AkzCtl ctl;
-    SSLAM_HIP_CHECK(sslam::copy_down(s, &n, o->n, 1));
-    SSLAM_HIP_CHECK(sslam::copy_down(s, &ctl, o->ctl, 1));
-    SSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    if (ctl.ncand > o->cand_cap || ctl.nkp > o->kp_cap) {
-        sslam::set_error("%s: the frame has %d candidates and %d keypoints before the quota, the instance holds max_candidates %d and "
-                         "max_keypoints %d: the frame is voided, nothing is truncated", who, ctl.ncand, ctl.nkp, o->cand_cap, o->kp_cap);
-        *n_out = 0;
-        return 3;
-    }
-    if (n > 0) {
-        SSLAM_HIP_CHECK(sslam::copy_down(s, xy_out, o->xy, (size_t)n * 2));
-        SSLAM_HIP_CHECK(sslam::copy_down(s, aux_out, o->aux, (size_t)n * 3));
-        SSLAM_HIP_CHECK(sslam::copy_down(s, lvl_out, o->lvl, (size_t)n * 2));
-        SSLAM_HIP_CHECK(sslam::copy_down(s, desc_out, o->desc, (size_t)n * AKZ_DESC_BYTES));
-        SSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    *n_out = n;
-    return 0;
+    return sslam::feat_detect_host(
+        who, o, img, h, w, c, "candidates",
+        [&](const uint8_t* img_dev) { return akaze_enqueue(o, img_dev, h, w, c, o->xy, o->aux, o->lvl, o->desc, o->n); },
+        {feat_rows(xy_out, o->xy, 2), feat_rows(aux_out, o->aux, 3), feat_rows(lvl_out, o->lvl, 2), feat_rows(desc_out, o->desc, AKZ_DESC_BYTES)},
+        n_out);
 }
 
 extern "C" int sslam_akaze_level_info(sslam_akaze* o, int level, int* info12) {

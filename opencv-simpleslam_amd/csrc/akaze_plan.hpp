@@ -13,11 +13,13 @@
 #include <cstdio>
 #include <vector>
 
+#include "feat_plan.hpp"
+
 namespace sslam {
 
 constexpr int AKZ_DESCRIPTOR_MLDB = 5, AKZ_DIFF_PM_G2 = 1;     // cv2's values
 constexpr int AKZ_MAX_OCTAVES = 8, AKZ_MAX_SUBLEVELS = 8, AKZ_MAX_LEVELS = AKZ_MAX_OCTAVES * AKZ_MAX_SUBLEVELS;
-constexpr int AKZ_MAX_SIDE = 16384;
+constexpr int AKZ_MAX_SIDE = FEAT_MAX_SIDE;
 constexpr int AKZ_MAX_POINTS = 1 << 20;
 constexpr int AKZ_MIN_OCTAVE_W = 80, AKZ_MIN_OCTAVE_H = 40;
 constexpr int AKZ_DESC_BYTES = 61, AKZ_DESC_BITS = 486;
@@ -71,12 +73,10 @@ struct AkzFed {                                                // of the paramet
 };
 
 struct AkzConsts {
-    float atan_p1, atan_p3, atan_p5, atan_p7, atan_eps, deg2rad;
+    FastAtan atan;
     float win_step, pi3, two_pi, five_pi3;
     float img_div, kfallback, koctave;
 };
-
-inline int akz_round(double v) { return (int)std::nearbyint(v); }      // cvRound: half to even
 
 // -> 0, or a non-zero code with the message written
 inline int akz_check_params(const AkzParams& p, int max_w, int max_h, char* msg, size_t n) {
@@ -89,14 +89,6 @@ inline int akz_check_params(const AkzParams& p, int max_w, int max_h, char* msg,
     if (p.diffusivity != AKZ_DIFF_PM_G2) { std::snprintf(msg, n, "diffusivity %d is not supported (only DIFF_PM_G2 = %d)", p.diffusivity, AKZ_DIFF_PM_G2); return 7; }
     if (!(p.max_points == -1 || (p.max_points >= 1 && p.max_points <= AKZ_MAX_POINTS))) { std::snprintf(msg, n, "max_points %d is neither -1 nor in 1..%d", p.max_points, AKZ_MAX_POINTS); return 8; }
     if (max_w < 1 || max_w > AKZ_MAX_SIDE || max_h < 1 || max_h > AKZ_MAX_SIDE) { std::snprintf(msg, n, "frame size %dx%d outside 1..%d", max_w, max_h, AKZ_MAX_SIDE); return 9; }
-    return 0;
-}
-
-// the per-call refusal: an image larger than the instance (never clipped)
-inline int akz_check_image(int w, int h, int c, int max_w, int max_h, char* msg, size_t n) {
-    if (c != 1 && c != 3 && c != 4) { std::snprintf(msg, n, "%d channels (want 1, 3 or 4)", c); return 1; }
-    if (w < 1 || h < 1) { std::snprintf(msg, n, "frame size %dx%d", w, h); return 2; }
-    if (w > max_w || h > max_h) { std::snprintf(msg, n, "frame %dx%d is larger than the instance's %dx%d", w, h, max_w, max_h); return 3; }
     return 0;
 }
 
@@ -117,7 +109,7 @@ inline AkzPlan akz_plan(const AkzParams& p, int w, int h) {
             L.octave = i; L.sublevel = j; L.w = lw; L.h = lh;
             L.esigma = AKZ_SOFFSET * std::pow(2.0, (double)j / p.nol + i);
             L.etime = 0.5 * (L.esigma * L.esigma);
-            L.sigma_size = akz_round(L.esigma * AKZ_DERIVATIVE_FACTOR / (1 << i));
+            L.sigma_size = cv_round(L.esigma * AKZ_DERIVATIVE_FACTOR / (1 << i));
             L.border = 2 * L.sigma_size + 1;
             L.size = (float)(2.0 * L.esigma * AKZ_DERIVATIVE_FACTOR); L.radius = (float)(L.esigma * AKZ_DERIVATIVE_FACTOR);
             L.ratio = (float)(1 << i); L.half = (float)(0.5 * ((1 << i) - 1));
@@ -126,7 +118,7 @@ inline AkzPlan akz_plan(const AkzParams& p, int w, int h) {
             L.off = P.plane_floats;
             P.plane_floats += (long long)lw * lh;
             const bool interior = lw > 2 * L.border && lh > 2 * L.border;
-            L.tx = interior ? (lw + AKZ_TILE_W - 1) / AKZ_TILE_W : 0; L.ty = interior ? (lh + AKZ_TILE_H - 1) / AKZ_TILE_H : 0;
+            L.tx = interior ? feat_cdiv(lw, AKZ_TILE_W) : 0; L.ty = interior ? feat_cdiv(lh, AKZ_TILE_H) : 0;
             P.max_tiles = std::max(P.max_tiles, L.tx * L.ty);
             L.one_wg = P.nlev > 0 && (long long)lw * lh <= AKZ_WG_PIXELS;
             ++P.nlev;
@@ -201,10 +193,7 @@ inline std::vector<float> akz_gauss_taps(double sigma) {
 
 inline AkzConsts akz_consts() {
     AkzConsts c{};
-    const float r2d = (float)(180.0 / M_PI);                   // fastAtan2's polynomial in degrees: ORB's
-    c.atan_p1 = 0.9997878412794807f * r2d; c.atan_p3 = -0.3258083974640975f * r2d; c.atan_p5 = 0.1555786518463281f * r2d;
-    c.atan_p7 = -0.04432655554792128f * r2d; c.atan_eps = 2.220446049250313e-16f;
-    c.deg2rad = (float)(M_PI / 180.0);
+    c.atan = fast_atan_consts();
     c.win_step = 0.15f; c.pi3 = (float)(M_PI / 3); c.two_pi = (float)(2 * M_PI); c.five_pi3 = (float)(5 * M_PI / 3);
     c.img_div = 255.f; c.kfallback = 0.03f; c.koctave = 0.75f;
     return c;

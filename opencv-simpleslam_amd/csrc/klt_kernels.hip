@@ -26,6 +26,8 @@
 // All loops are bounded: levels <= KLT_MAX_LEVELS, iterations <= 100, window elements <= 31 x 31.
 // PARITY UNPINNED: cv2 is absent here; tests/klt_ref.py restates the functions and names what could not be confirmed.
 #include "common.hpp"
+#include "feat_device.hpp"
+#include "feat_host.hpp"
 
 #include <cmath>
 
@@ -33,7 +35,7 @@
 
 namespace {
 
-constexpr int KLT_MAX_SIDE = 16384;
+constexpr int KLT_MAX_SIDE = sslam::FEAT_MAX_SIDE;
 constexpr int KLT_MAX_POINTS = 1 << 20;
 constexpr int KLT_MIN_WIN = 3, KLT_MAX_WIN = 31;         // odd sides; 31 x 31 x 3 int16 per wave is the LDS patch
 constexpr int KLT_MAX_ELEMS = KLT_MAX_WIN * KLT_MAX_WIN;
@@ -70,27 +72,12 @@ struct sslam_klt {
 
 namespace {
 
-__device__ __forceinline__ int klt_reflect101(int i, int n) {
-    if (n == 1) return 0;
-    const int p = 2 * (n - 1);
-    i %= p;
-    if (i < 0) i += p;
-    return i < n ? i : p - i;
-}
-
 __global__ __launch_bounds__(KLT_T)
 void klt_gray_kernel(const uint8_t* __restrict__ src, int h, int w, int C, uint8_t* __restrict__ dst, int stride) {
     const size_t p = (size_t)blockIdx.x * KLT_T + threadIdx.x;
     if (p >= (size_t)h * w) return;
     const int y = (int)(p / (size_t)w), x = (int)(p % (size_t)w);
-    int v;
-    if (C == 1) {
-        v = src[p];
-    } else {
-        const uint8_t* s = src + p * (size_t)C;
-        v = ((int)s[0] * 3735 + (int)s[1] * 19235 + (int)s[2] * 9798 + (1 << 14)) >> 15;
-    }
-    dst[(size_t)y * stride + x] = (uint8_t)v;
+    dst[(size_t)y * stride + x] = (uint8_t)sslam::bgr_to_grey(src + p * (size_t)C, C);
 }
 
 // src / dst: the interiors (pointer to pixel (0, 0)) of two padded levels
@@ -103,11 +90,11 @@ void klt_down_kernel(const uint8_t* __restrict__ src, int sh, int sw, int sstrid
     const int k[5] = {1, 4, 6, 4, 1};
     int cx[5];
 #pragma unroll
-    for (int i = 0; i < 5; ++i) cx[i] = klt_reflect101(2 * x - 2 + i, sw);
+    for (int i = 0; i < 5; ++i) cx[i] = sslam::reflect101(2 * x - 2 + i, sw);
     int sum = 128;
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
-        const uint8_t* r = src + (size_t)klt_reflect101(2 * y - 2 + j, sh) * sstride;
+        const uint8_t* r = src + (size_t)sslam::reflect101(2 * y - 2 + j, sh) * sstride;
         int row = 0;
 #pragma unroll
         for (int i = 0; i < 5; ++i) row += k[i] * (int)r[cx[i]];
@@ -124,8 +111,8 @@ void klt_ring_deriv_kernel(uint8_t* __restrict__ img, uint32_t* __restrict__ der
     const int y = (int)(p / (size_t)stride) - ph, x = (int)(p % (size_t)stride) - pw;
     const uint8_t* in = img + (size_t)ph * stride + pw;                      // pixel (0, 0)
     if (y >= 0 && y < h && x >= 0 && x < w) {
-        const int ym = klt_reflect101(y - 1, h), yp = klt_reflect101(y + 1, h);
-        const int xm = klt_reflect101(x - 1, w), xp = klt_reflect101(x + 1, w);
+        const int ym = sslam::reflect101(y - 1, h), yp = sslam::reflect101(y + 1, h);
+        const int xm = sslam::reflect101(x - 1, w), xp = sslam::reflect101(x + 1, w);
         const uint8_t* r0 = in + (size_t)ym * stride;
         const uint8_t* r1 = in + (size_t)y * stride;
         const uint8_t* r2 = in + (size_t)yp * stride;
@@ -134,7 +121,7 @@ void klt_ring_deriv_kernel(uint8_t* __restrict__ img, uint32_t* __restrict__ der
         const int dy = 3 * (g - a) + 10 * (hh - b) + 3 * (i - c);
         der[p] = (uint32_t)(uint16_t)(int16_t)dx | ((uint32_t)(uint16_t)(int16_t)dy << 16);
     } else {
-        img[p] = in[(size_t)klt_reflect101(y, h) * stride + klt_reflect101(x, w)];
+        img[p] = in[(size_t)sslam::reflect101(y, h) * stride + sslam::reflect101(x, w)];
         der[p] = 0u;
     }
 }
@@ -178,12 +165,6 @@ __device__ __forceinline__ void klt_next(int& x, int& y, int step_x, int step_y,
 }
 
 __device__ __forceinline__ int klt_descale(int v, int n) { return (v + (1 << (n - 1))) >> n; }
-
-__device__ __forceinline__ long long klt_wave_sum(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // an exact integer below 2^53 -> float32, one rounding
 __device__ __forceinline__ float klt_to_float(long long s) { return (float)(double)s; }
@@ -256,7 +237,7 @@ __global__ __launch_bounds__(KLT_T) void klt_track_kernel(KltTrackArgs a) {
                 sI[e] = (int16_t)iv; sIx[e] = (int16_t)ixv; sIy[e] = (int16_t)iyv;
                 s11 += (long long)(ixv * ixv); s12 += (long long)(ixv * iyv); s22 += (long long)(iyv * iyv);
             }
-            s11 = klt_wave_sum(s11); s12 = klt_wave_sum(s12); s22 = klt_wave_sum(s22);
+            s11 = sslam::wave_sum(s11); s12 = sslam::wave_sum(s12); s22 = sslam::wave_sum(s22);
             const float A11 = klt_to_float(s11) * FLT_SCALE, A12 = klt_to_float(s12) * FLT_SCALE, A22 = klt_to_float(s22) * FLT_SCALE;
             const float D = A11 * A22 - A12 * A12;
             const float dif = A11 - A22;
@@ -281,7 +262,7 @@ __global__ __launch_bounds__(KLT_T) void klt_track_kernel(KltTrackArgs a) {
                     const int diff = klt_sample_img(LJ, ww, wh, u, x, y) - (int)sI[e];
                     sb1 += (long long)(diff * (int)sIx[e]); sb2 += (long long)(diff * (int)sIy[e]);
                 }
-                sb1 = klt_wave_sum(sb1); sb2 = klt_wave_sum(sb2);
+                sb1 = sslam::wave_sum(sb1); sb2 = sslam::wave_sum(sb2);
                 const float b1 = klt_to_float(sb1) * FLT_SCALE, b2 = klt_to_float(sb2) * FLT_SCALE;
                 const float dx = (A12 * b2 - A22 * b1) * Dinv, dy = (A12 * b1 - A11 * b2) * Dinv;
                 cx = cx + dx; cy = cy + dy;
@@ -304,7 +285,7 @@ __global__ __launch_bounds__(KLT_T) void klt_track_kernel(KltTrackArgs a) {
                         const int diff = klt_sample_img(LJ, ww, wh, u, x, y) - (int)sI[e];
                         se += (long long)(diff < 0 ? -diff : diff);
                     }
-                    se = klt_wave_sum(se);
+                    se = sslam::wave_sum(se);
                     err = klt_div(klt_to_float(se), den_err);
                 }
             }
@@ -521,13 +502,10 @@ extern "C" int sslam_klt_push_dev(sslam_klt* k, const uint8_t* img, int h, int w
 extern "C" int sslam_klt_push_host(sslam_klt* k, const uint8_t* img, int h, int w, int c) {
     if (int rc = klt_check_image("sslam_klt_push_host", k, img, h, w, c)) return rc;
     SSLAM_HIP_CHECK(hipSetDevice(k->ctx->device));
-    const size_t bytes = (size_t)h * w * c;
-    char* b;
-    if (int rc = sslam::ctx_scratch(k->ctx, bytes, &b)) return rc;
-    hipStream_t s = k->ctx->stream;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b, img, bytes, hipMemcpyHostToDevice, s));
-    if (int rc = klt_enqueue_push(k, (const uint8_t*)b, h, w, c)) return rc;
-    SSLAM_HIP_CHECK(hipStreamSynchronize(s));            // the caller's image has been read, the scratch slab is free again
+    const uint8_t* img_dev;
+    if (int rc = sslam::feat_stage_image(k->ctx, img, h, w, c, &img_dev)) return rc;
+    if (int rc = klt_enqueue_push(k, img_dev, h, w, c)) return rc;
+    SSLAM_HIP_CHECK(hipStreamSynchronize(k->ctx->stream));            // the caller's image has been read, the scratch slab is free again
     return 0;
 }
 

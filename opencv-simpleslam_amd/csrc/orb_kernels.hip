@@ -37,6 +37,8 @@
 // plan constants or by device counts clamped to those capacities.
 // PARITY UNPINNED: cv2 is absent here; tests/orb_ref.py names what could not be confirmed.
 #include "common.hpp"
+#include "feat_device.hpp"
+#include "feat_host.hpp"
 #include "geom_common.hpp"
 #include "orb_plan.hpp"
 
@@ -74,7 +76,9 @@ struct OrbArgs {
     OrbLevelDev lv[ORB_MAX_LEVELS];
     unsigned long long umax4;                    // umax[v] in bits 4 v .. 4 v + 3
     int gauss[7];
-    float harris_k, harris_scale4, atan_p1, atan_p3, atan_p5, atan_p7, atan_eps, deg2rad, patch_size;
+    float harris_k, harris_scale4;
+    FastAtan atan;
+    float patch_size;
     uint8_t* img; uint8_t* blur;                 // the two slabs
     uint32_t* cand_xy; uint32_t* cand_score; uint32_t* cand_key;      // [cand_total]
     unsigned long long* skey;                    // [cand_total] the survivors' output keys: ~response key << 32 | y << 16 | x
@@ -82,16 +86,6 @@ struct OrbArgs {
     const int8_t* pattern;                       // [512][2]
     float* xy_out; float* aux_out; uint8_t* desc_out; int32_t* n_out;
 };
-
-__device__ __forceinline__ int orb_reflect101(int i, int n) {
-    const int once = i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i);        // one fold is enough unless the border exceeds the level
-    if ((unsigned)once < (unsigned)n) return once;
-    if (n == 1) return 0;
-    const int p = 2 * (n - 1);
-    i %= p;
-    if (i < 0) i += p;
-    return i < n ? i : p - i;
-}
 
 // the source tap and its 8-bit weight of INTER_LINEAR_EXACT along one axis: the exact rational ((2 d + 1) sn - dn) / (2 dn)
 __device__ __forceinline__ void orb_tap(int d, int sn, int dn, int& s0, int& s1, int& c) {
@@ -108,11 +102,11 @@ __global__ __launch_bounds__(ORB_T) void orb_level_kernel(OrbArgs a, int l, cons
     const int px = blockIdx.x * 64 + (threadIdx.x & 63), py = blockIdx.y * (ORB_T / 64) + (threadIdx.x >> 6);
     if (px >= L.stride || py >= L.rows) return;
     const int p = py * L.stride + px;
-    const int x = orb_reflect101(px - a.border, L.w), y = orb_reflect101(py - a.border, L.h);
+    const int x = reflect101(px - a.border, L.w), y = reflect101(py - a.border, L.h);
     int v;
     if (l == 0) {
         const uint8_t* s = src + ((size_t)y * L.w + x) * C;
-        v = C == 1 ? (int)s[0] : ((int)s[0] * 3735 + (int)s[1] * 19235 + (int)s[2] * 9798 + (1 << 14)) >> 15;
+        v = bgr_to_grey(s, C);
     } else {
         const OrbLevelDev S = a.lv[l - 1];
         const uint8_t* s = a.img + S.off + (size_t)a.border * S.stride + a.border;
@@ -237,7 +231,7 @@ __global__ __launch_bounds__(ORB_T) void orb_blur_kernel(OrbArgs a) {
     const int tile = blockIdx.x - L.pad_base;
     const int px = (tile % L.pad_tx) * ORB_TILE_W + (tid & (ORB_TILE_W - 1)), py = (tile / L.pad_tx) * ORB_TILE_H + tid / ORB_TILE_W;
     if (px >= L.stride || py >= L.rows) return;
-    const int x = orb_reflect101(px - a.border, L.w), y = orb_reflect101(py - a.border, L.h);
+    const int x = reflect101(px - a.border, L.w), y = reflect101(py - a.border, L.h);
     const uint8_t* c = a.img + L.off + (size_t)(y + a.border) * L.stride + (x + a.border);
     int v = 0;
 #pragma unroll
@@ -423,12 +417,6 @@ __global__ __launch_bounds__(ORB_SEL_T) void orb_select_kernel(OrbArgs a) {
 }
 
 // ---- rank, orientation, descriptor, output: a keypoint per wavefront ---------------------------------------------------
-__device__ __forceinline__ int orb_wave_sum(int v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __global__ __launch_bounds__(ORB_T) void orb_describe_kernel(OrbArgs a) {
     const int l = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const OrbLevelDev L = a.lv[l];
@@ -448,7 +436,7 @@ __global__ __launch_bounds__(ORB_T) void orb_describe_kernel(OrbArgs a) {
         int less = 0;
 #pragma unroll 4
         for (int jj = lane; jj < n; jj += 64) less += skey[jj] < mine;
-        const int pos = first + orb_wave_sum(less);
+        const int pos = first + wave_sum(less);
         const int x = (int)(xy & 0xffffu), y = (int)(xy >> 16);
         const size_t centre = (size_t)(y + a.border) * L.stride + (x + a.border);
         // the intensity centroid over the disc: rows v = -15 .. 15 of half width umax[|v|]
@@ -461,26 +449,9 @@ __global__ __launch_bounds__(ORB_T) void orb_describe_kernel(OrbArgs a) {
                 m10 += u * val; m01 += v * val;
             }
         }
-        m01 = orb_wave_sum(m01); m10 = orb_wave_sum(m10);
-        // fastAtan2((float)m01, (float)m10), degrees
-        const float fy = (float)m01, fx = (float)m10;
-        const float ax = fabsf(fx), ay = fabsf(fy);
-        float ang;
-        if (ax >= ay) {
-            const float den = ax + a.atan_eps;
-            const float q = (float)((double)ay / (double)den), q2 = q * q;
-            float t = a.atan_p7 * q2; t = t + a.atan_p5; t = t * q2; t = t + a.atan_p3; t = t * q2; t = t + a.atan_p1;
-            ang = t * q;
-        } else {
-            const float den = ay + a.atan_eps;
-            const float q = (float)((double)ax / (double)den), q2 = q * q;
-            float t = a.atan_p7 * q2; t = t + a.atan_p5; t = t * q2; t = t + a.atan_p3; t = t * q2; t = t + a.atan_p1;
-            t = t * q;
-            ang = 90.f - t;
-        }
-        if (fx < 0.f) ang = 180.f - ang;
-        if (fy < 0.f) ang = 360.f - ang;
-        const float rad = ang * a.deg2rad;
+        m01 = wave_sum(m01); m10 = wave_sum(m10);
+        const float ang = fast_atan2_deg(a.atan, (float)m01, (float)m10);
+        const float rad = ang * a.atan.deg2rad;
         const float ca = (float)cos((double)rad), sa = (float)sin((double)rad);
         const uint8_t* bl = a.blur + L.off + centre;
         for (int k = 0; k < 4; ++k) {
@@ -566,8 +537,7 @@ int orb_enqueue(sslam_orb* o, const uint8_t* img_dev, int h, int w, int c, float
     }
     for (int v = 0; v <= ORB_HALF; ++v) a.umax4 |= (unsigned long long)P.umax[v] << (4 * v);
     for (int i = 0; i < 7; ++i) a.gauss[i] = P.gauss[i];
-    a.harris_k = P.harris_k; a.harris_scale4 = P.harris_scale4; a.atan_p1 = P.atan_p1; a.atan_p3 = P.atan_p3; a.atan_p5 = P.atan_p5;
-    a.atan_p7 = P.atan_p7; a.atan_eps = P.atan_eps; a.deg2rad = P.deg2rad; a.patch_size = P.patch_size;
+    a.harris_k = P.harris_k; a.harris_scale4 = P.harris_scale4; a.atan = P.atan; a.patch_size = P.patch_size;
     a.img = o->img; a.blur = o->blur; a.cand_xy = o->cand_xy; a.cand_score = o->cand_score; a.cand_key = o->cand_key; a.skey = o->skey;
     a.ctl = o->ctl; a.pattern = o->pattern; a.xy_out = xy; a.aux_out = aux; a.desc_out = desc; a.n_out = n_out;
     for (int l = 0; l < P.nactive; ++l)
@@ -578,14 +548,6 @@ int orb_enqueue(sslam_orb* o, const uint8_t* img_dev, int h, int w, int c, float
     hipLaunchKernelGGL(orb_select_kernel, dim3(P.nactive), dim3(ORB_SEL_T), 0, s, a);
     hipLaunchKernelGGL(orb_describe_kernel, dim3(ORB_DESC_GX, P.nactive), dim3(ORB_T), 0, s, a);
     SSLAM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-int orb_check_call(const char* who, sslam_orb* o, const void* img, int h, int w, int c) {
-    SSLAM_REQUIRE(o != nullptr, "%s: instance is NULL", who);
-    SSLAM_REQUIRE(img != nullptr, "%s: img is NULL", who);
-    char msg[160];
-    if (orb_check_image(w, h, c, o->max_w, o->max_h, msg, sizeof msg)) { sslam::set_error("%s: %s", who, msg); return 2; }
     return 0;
 }
 
@@ -643,7 +605,7 @@ extern "C" int sslam_orb_default_pattern(int8_t* pattern_out) {
 extern "C" int sslam_orb_detect_dev(sslam_orb* o, const uint8_t* img_dev, int h, int w, int c, float* xy_out_dev,
                                     float* aux_out_dev, uint8_t* desc_out_dev, int32_t* n_out_dev) {
     const char* who = "sslam_orb_detect_dev";
-    if (int rc = orb_check_call(who, o, img_dev, h, w, c)) return rc;
+    if (int rc = feat_check_call(who, o, img_dev, h, w, c)) return rc;
     SSLAM_REQUIRE(xy_out_dev && aux_out_dev && desc_out_dev && n_out_dev, "%s: an output pointer is NULL", who);
     SSLAM_HIP_CHECK(hipSetDevice(o->ctx->device));
     return orb_enqueue(o, img_dev, h, w, c, xy_out_dev, aux_out_dev, desc_out_dev, n_out_dev);
@@ -652,17 +614,16 @@ extern "C" int sslam_orb_detect_dev(sslam_orb* o, const uint8_t* img_dev, int h,
 extern "C" int sslam_orb_detect_host(sslam_orb* o, const uint8_t* img, int h, int w, int c, float* xy_out, float* aux_out,
                                      uint8_t* desc_out, int32_t* n_out) {
     const char* who = "sslam_orb_detect_host";
-    if (int rc = orb_check_call(who, o, img, h, w, c)) return rc;
+    if (int rc = feat_check_call(who, o, img, h, w, c)) return rc;
     SSLAM_REQUIRE(xy_out && aux_out && desc_out && n_out, "%s: an output pointer is NULL", who);
     SSLAM_HIP_CHECK(hipSetDevice(o->ctx->device));
-    const size_t bytes = (size_t)h * w * c;
-    char* b;
-    if (int rc = sslam::ctx_scratch(o->ctx, bytes, &b)) return rc;
+    const uint8_t* img_dev;
+    if (int rc = feat_stage_image(o->ctx, img, h, w, c, &img_dev)) return rc;
+    if (int rc = orb_enqueue(o, img_dev, h, w, c, o->xy, o->aux, o->desc, o->n)) return rc;
     hipStream_t s = o->ctx->stream;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b, img, bytes, hipMemcpyHostToDevice, s));
-    if (int rc = orb_enqueue(o, (const uint8_t*)b, h, w, c, o->xy, o->aux, o->desc, o->n)) return rc;
     // the count and the rows a call without ties can fill come down behind the kernels: one synchronisation.  Only a call
-    // whose ties exceed that fetches the rest.
+    // whose ties exceed that fetches the rest.  (ORB has no capacities to void a frame on and knows its likely count in advance:
+    // this is why its tail is not feat_host.hpp's feat_detect_host, which reads the count first and fetches the rows after.)
     const size_t first = (size_t)std::min<long long>(o->cap, (long long)o->p.nfeatures + 64);
     int32_t n = 0;
     SSLAM_HIP_CHECK(sslam::copy_down(s, &n, o->n, 1));

@@ -1,6 +1,6 @@
 // orb_plan.hpp - everything the host decides about an ORB instance and about one call on it, decided ONCE: the parameter
 // refusals, the level scales, sizes, strides and slab offsets (interior and border), the per-level quotas, the `umax` table,
-// the blur taps, the float constants of the response and of fastAtan2, the candidate capacities, the per-level tile tables of
+// the blur taps, the float constants of the response, the candidate capacities, the per-level tile tables of
 // the all-level launches, the default sampling pattern.  Plain C++17 with no HIP include: tests/test_orb_plan.py compiles it
 // with the host compiler and compares it with tests/orb_ref.py.  orb_kernels.hip launches from these fields and holds no
 // size arithmetic of its own.  Semantics and what is unconfirmed without cv2: tests/orb_ref.py.
@@ -11,10 +11,12 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "feat_plan.hpp"
+
 namespace sslam {
 
 constexpr int ORB_MAX_LEVELS = 16;
-constexpr int ORB_MAX_SIDE = 16384;
+constexpr int ORB_MAX_SIDE = FEAT_MAX_SIDE;
 constexpr int ORB_MAX_FEATURES = 1 << 20;
 constexpr int ORB_PATCH = 31, ORB_HALF = 15;   // patchSize and its half: the disc of the orientation, the pattern's range
 constexpr int ORB_HARRIS_BLOCK = 7;
@@ -26,10 +28,6 @@ constexpr int ORB_SEL_T = 1024;                // the select workgroup, one per 
 constexpr int ORB_SEL_K = 8;                   // ... and the keys a thread holds per turn
 constexpr int ORB_RESP_GX = 32;                // response workgroups per level (grid-stride over the device count)
 constexpr int ORB_DESC_GX = 512;               // describe workgroups per level, four keypoints (wavefronts) each
-
-constexpr int orb_cdiv(int a, int b) { return (a + b - 1) / b; }
-inline int orb_round(double v) { return (int)std::nearbyint(v); }        // cvRound: half to even
-inline int orb_roundf(float v) { return (int)std::nearbyintf(v); }
 
 struct OrbParams {
     int nfeatures = 500;
@@ -61,7 +59,8 @@ struct OrbPlan {
     int umax[ORB_HALF + 1];
     int gauss[7];
     float harris_k, harris_scale4;
-    float atan_p1, atan_p3, atan_p5, atan_p7, atan_eps, deg2rad, patch_size;
+    FastAtan atan;                 // fastAtan2's polynomial (feat_plan.hpp)
+    float patch_size;
 };
 
 // -> 0, or a non-zero code with the message written
@@ -105,7 +104,7 @@ inline void orb_quotas(const OrbParams& p, int* out) {
     nd = nd / den;
     int sum = 0;
     for (int l = 0; l < p.nlevels - 1; ++l) {
-        out[l] = orb_roundf(nd);
+        out[l] = cv_roundf(nd);
         sum += out[l];
         nd = nd * factor;
     }
@@ -124,8 +123,8 @@ inline OrbPlan orb_plan(const OrbParams& p, int w, int h) {
         OrbLevel& L = P.lv[l];
         L.scale = (float)std::pow(sf, (double)l);
         const float inv = 1.0f / L.scale;
-        L.w = orb_roundf((float)w * inv);
-        L.h = orb_roundf((float)h * inv);
+        L.w = cv_roundf((float)w * inv);
+        L.h = cv_roundf((float)h * inv);
         L.quota = quota[l];
         L.cut1_n = p.score_type == 0 ? 2 * quota[l] : quota[l];
         alive = alive && L.w >= need && L.h >= need;
@@ -134,11 +133,11 @@ inline OrbPlan orb_plan(const OrbParams& p, int w, int h) {
         L.stride = L.w + 2 * P.border; L.rows = L.h + 2 * P.border;
         L.off = P.slab_bytes;
         P.slab_bytes += ((long long)L.stride * L.rows + 255) / 256 * 256;
-        L.fast_tx = orb_cdiv(L.w, ORB_FAST_W); L.fast_ty = orb_cdiv(L.h, ORB_FAST_H); L.fast_base = P.fast_tiles;
+        L.fast_tx = feat_cdiv(L.w, ORB_FAST_W); L.fast_ty = feat_cdiv(L.h, ORB_FAST_H); L.fast_base = P.fast_tiles;
         P.fast_tiles += L.fast_tx * L.fast_ty;
-        L.pad_tx = orb_cdiv(L.stride, ORB_TILE_W); L.pad_ty = orb_cdiv(L.rows, ORB_TILE_H); L.pad_base = P.blur_tiles;
+        L.pad_tx = feat_cdiv(L.stride, ORB_TILE_W); L.pad_ty = feat_cdiv(L.rows, ORB_TILE_H); L.pad_base = P.blur_tiles;
         P.blur_tiles += L.pad_tx * L.pad_ty;
-        L.cand_cap = orb_cdiv(L.w, 2) * orb_cdiv(L.h, 2);
+        L.cand_cap = feat_cdiv(L.w, 2) * feat_cdiv(L.h, 2);
         L.cand_off = P.cand_total;
         P.cand_total += L.cand_cap;
         P.nactive = l + 1;
@@ -146,7 +145,7 @@ inline OrbPlan orb_plan(const OrbParams& p, int w, int h) {
     // umax: the half-widths of the disc's rows, OpenCV's table with its symmetry fix-up
     const int vmax = (int)std::floor(ORB_HALF * std::sqrt(2.0) / 2 + 1), vmin = (int)std::ceil(ORB_HALF * std::sqrt(2.0) / 2);
     int um[ORB_HALF + 2] = {};
-    for (int v = 0; v <= vmax; ++v) um[v] = orb_round(std::sqrt((double)ORB_HALF * ORB_HALF - (double)v * v));
+    for (int v = 0; v <= vmax; ++v) um[v] = cv_round(std::sqrt((double)ORB_HALF * ORB_HALF - (double)v * v));
     for (int v = ORB_HALF, v0 = 0; v >= vmin; --v) {
         while (um[v0] == um[v0 + 1]) ++v0;
         um[v] = v0;
@@ -157,17 +156,13 @@ inline OrbPlan orb_plan(const OrbParams& p, int w, int h) {
     double g[7], gs = 0;
     for (int i = 0; i < 7; ++i) { g[i] = std::exp(-(double)((i - 3) * (i - 3)) / (2 * 2.0 * 2.0)); gs += g[i]; }
     int ks = 0;
-    for (int i = 0; i < 7; ++i) { P.gauss[i] = orb_round(g[i] / gs * 256); ks += P.gauss[i]; }
+    for (int i = 0; i < 7; ++i) { P.gauss[i] = cv_round(g[i] / gs * 256); ks += P.gauss[i]; }
     P.gauss[3] += 256 - ks;
     P.harris_k = 0.04f;
     const float hs = 1.0f / (float)(4 * ORB_HARRIS_BLOCK * 255);
     float s4 = hs * hs; s4 = s4 * hs; s4 = s4 * hs;
     P.harris_scale4 = s4;
-    const float r2d = (float)(180 / 3.14159265358979323846);
-    P.atan_p1 = 0.9997878412794807f * r2d; P.atan_p3 = -0.3258083974640975f * r2d;
-    P.atan_p5 = 0.1555786518463281f * r2d; P.atan_p7 = -0.04432655554792128f * r2d;
-    P.atan_eps = (float)2.2204460492503131e-16;
-    P.deg2rad = (float)(3.14159265358979323846 / 180.0);
+    P.atan = fast_atan_consts();
     P.patch_size = (float)ORB_PATCH;
     return P;
 }
@@ -175,13 +170,5 @@ inline OrbPlan orb_plan(const OrbParams& p, int w, int h) {
 // the bound on the output rows of any call on an instance made for max_w x max_h: every level's NMS bound (ties are never
 // dropped, so nfeatures does not bound them)
 inline long long orb_capacity(const OrbParams& p, int max_w, int max_h) { return std::max(orb_plan(p, max_w, max_h).cand_total, 1LL); }
-
-// the per-call refusal: an image larger than the instance (never clipped)
-inline int orb_check_image(int w, int h, int c, int max_w, int max_h, char* msg, size_t n) {
-    if (c != 1 && c != 3 && c != 4) { std::snprintf(msg, n, "%d channels (want 1, 3 or 4)", c); return 1; }
-    if (w < 1 || h < 1) { std::snprintf(msg, n, "frame size %dx%d", w, h); return 2; }
-    if (w > max_w || h > max_h) { std::snprintf(msg, n, "frame %dx%d is larger than the instance's %dx%d", w, h, max_w, max_h); return 3; }
-    return 0;
-}
 
 }  // namespace sslam

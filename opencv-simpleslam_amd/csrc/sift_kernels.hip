@@ -38,6 +38,8 @@
 // (bounded by sigma <= 8 and the image diagonal) or by device counts clamped to the capacities.
 // PARITY UNPINNED: cv2 is absent here; tests/sift_ref.py names what could not be confirmed.
 #include "common.hpp"
+#include "feat_device.hpp"
+#include "feat_host.hpp"
 #include "geom_common.hpp"
 #include "sift_plan.hpp"
 
@@ -80,15 +82,6 @@ struct SiftArgs {
     float* xy_out; float* aux_out; int32_t* oct_out; float* desc_out; int32_t* n_out;
 };
 
-__device__ __forceinline__ int sift_reflect101(int i, int n) {
-    if ((unsigned)i < (unsigned)n) return i;
-    if (n == 1) return 0;
-    const int p = 2 * (n - 1);
-    i %= p;
-    if (i < 0) i += p;
-    return i < n ? i : p - i;
-}
-
 // ---- the base image ---------------------------------------------------------------------------------------------------
 // INTER_LINEAR at scale 2: destination d reads source (d + 0.5) / 2 - 0.5 = s + f with f = 0.75 (d even, s = d / 2 - 1) or 0.25
 // (d odd, s = (d - 1) / 2); a tap outside the source clamps with weight 0
@@ -100,9 +93,7 @@ __device__ __forceinline__ void sift_up_tap(int d, int n, int& s0, int& s1, floa
     s0 = s; s1 = min(s + 1, n - 1);
 }
 
-__device__ __forceinline__ float sift_grey(const uint8_t* __restrict__ s, int C) {
-    return (float)(C == 1 ? (int)s[0] : ((int)s[0] * 3735 + (int)s[1] * 19235 + (int)s[2] * 9798 + (1 << 14)) >> 15);
-}
+__device__ __forceinline__ float sift_grey(const uint8_t* __restrict__ s, int C) { return (float)bgr_to_grey(s, C); }
 
 __global__ __launch_bounds__(SIFT_T) void sift_base_kernel(const uint8_t* __restrict__ src, int w, int h, int C, float* __restrict__ dst) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * SIFT_WAVES + (threadIdx.x >> 6);
@@ -150,7 +141,7 @@ __device__ __forceinline__ void sift_blur_row_at(const float* __restrict__ src, 
     const float* row = src + (size_t)y * w;
     const int first = x0 - (n >> 1);
     float acc[SIFT_BLUR_R] = {};
-    sift_blur_run([&](int m) { return row[sift_reflect101(first + m, w)]; }, taps, n, acc);
+    sift_blur_run([&](int m) { return row[reflect101(first + m, w)]; }, taps, n, acc);
 #pragma unroll
     for (int j = 0; j < SIFT_BLUR_R; ++j)
         if (x0 + j < w) dst[(size_t)y * w + x0 + j] = acc[j];
@@ -161,7 +152,7 @@ __device__ __forceinline__ void sift_blur_col_at(const float* __restrict__ src, 
                                                  int n, const float* prev, float* __restrict__ dog, float* also, int x, int y0) {
     const int first = y0 - (n >> 1);
     float acc[SIFT_BLUR_R] = {};
-    sift_blur_run([&](int m) { return src[(size_t)sift_reflect101(first + m, h) * w + x]; }, taps, n, acc);
+    sift_blur_run([&](int m) { return src[(size_t)reflect101(first + m, h) * w + x]; }, taps, n, acc);
 #pragma unroll
     for (int j = 0; j < SIFT_BLUR_R; ++j)
         if (y0 + j < h) {
@@ -274,32 +265,7 @@ __global__ __launch_bounds__(SIFT_T) void sift_extrema_kernel(SiftArgs a) {
 }
 
 // ---- refinement and orientation: a candidate per wavefront -----------------------------------------------------------------
-__device__ __forceinline__ float sift_atan2(const SiftConsts& k, float fy, float fx) {
-    const float ax = fabsf(fx), ay = fabsf(fy);
-    float ang;
-    if (ax >= ay) {
-        const float q = ay / (ax + k.atan_eps), q2 = q * q;
-        float t = k.atan_p7 * q2; t = t + k.atan_p5; t = t * q2; t = t + k.atan_p3; t = t * q2; t = t + k.atan_p1;
-        ang = t * q;
-    } else {
-        const float q = ax / (ay + k.atan_eps), q2 = q * q;
-        float t = k.atan_p7 * q2; t = t + k.atan_p5; t = t * q2; t = t + k.atan_p3; t = t * q2; t = t + k.atan_p1;
-        t = t * q;
-        ang = 90.f - t;
-    }
-    if (fx < 0.f) ang = 180.f - ang;
-    if (fy < 0.f) ang = 360.f - ang;
-    return ang;
-}
-
 __device__ __forceinline__ float sift_exp(float x) { return (float)exp((double)x); }
-
-__device__ __forceinline__ unsigned long long sift_fixed(float v) {     // v >= 0
-    return (unsigned long long)((double)v * (double)(1ull << SIFT_HIST_SCALE_LOG2));
-}
-__device__ __forceinline__ float sift_unfixed(unsigned long long s) {
-    return (float)((double)(long long)s / (double)(1ull << SIFT_HIST_SCALE_LOG2));
-}
 
 // cv::LU on a 3 x 3 float32 system, partial pivoting; x = 0 for a singular one
 __device__ __forceinline__ void sift_solve3(float A[3][3], float b[3], float eps) {
@@ -413,17 +379,17 @@ __global__ __launch_bounds__(SIFT_T) __attribute__((target("no-packed-fp32-ops")
             const float* g = G + (size_t)y * O.w + x;
             const float dx = g[1] - g[-1], dy = g[-O.w] - g[O.w];
             const float wgt = sift_exp((float)(i * i + j * j) * escale);
-            const float ori = sift_atan2(K, dy, dx);
+            const float ori = fast_atan2_deg(K.atan, dy, dx);
             const float xx = dx * dx, yy = dy * dy;
             const float mag = sqrtf(xx + yy);
             int bin = (int)rintf((float)SIFT_ORI_BINS / 360.f * ori);
             if (bin >= SIFT_ORI_BINS) bin -= SIFT_ORI_BINS;
             if (bin < 0) bin += SIFT_ORI_BINS;
-            if ((unsigned)bin < (unsigned)SIFT_ORI_BINS) atomicAdd(&s_acc[wave][bin], sift_fixed(wgt * mag));
+            if ((unsigned)bin < (unsigned)SIFT_ORI_BINS) atomicAdd(&s_acc[wave][bin], to_fixed<SIFT_HIST_SCALE_LOG2, unsigned long long>(wgt * mag));
         }
         __builtin_amdgcn_wave_barrier();
         __threadfence_block();
-        if (lane < SIFT_ORI_BINS) s_raw[wave][lane] = sift_unfixed(s_acc[wave][lane]);
+        if (lane < SIFT_ORI_BINS) s_raw[wave][lane] = from_fixed<SIFT_HIST_SCALE_LOG2>(s_acc[wave][lane]);
         __builtin_amdgcn_wave_barrier();
         __threadfence_block();
         const int n36 = SIFT_ORI_BINS;
@@ -485,16 +451,8 @@ __device__ __forceinline__ SiftKey sift_key(const uint32_t* __restrict__ kp, int
 
 __device__ __forceinline__ bool sift_same4(const SiftKey& p, const SiftKey& q) { return p.x == q.x && p.y == q.y && p.size == q.size && p.ang == q.ang; }
 
-__device__ __forceinline__ int sift_wave_sum(int v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ bool sift_void(const SiftArgs& a) { return a.ctl->ncand > a.cand_cap || a.ctl->nkp > a.kp_cap; }
-
 __global__ __launch_bounds__(SIFT_T) void sift_dup_kernel(SiftArgs a) {
-    if (sift_void(a)) return;
+    if (feat_voided(a)) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = a.ctl->nkp;
     for (int j = blockIdx.x * SIFT_WAVES + wave; j < n; j += gridDim.x * SIFT_WAVES) {
         const SiftKey me = sift_key(a.kp, j);
@@ -503,13 +461,13 @@ __global__ __launch_bounds__(SIFT_T) void sift_dup_kernel(SiftArgs a) {
             const SiftKey q = sift_key(a.kp, i);
             before += i != j && sift_same4(q, me) && (q.resp > me.resp || (q.resp == me.resp && (q.oct > me.oct || (q.oct == me.oct && i < j))));
         }
-        before = sift_wave_sum(before);
+        before = wave_sum(before);
         if (lane == 0) { a.flag[j] = before ? 1 : 0; a.rkey[j] = before ? -1.f : me.resp; }
     }
 }
 
 __global__ __launch_bounds__(SIFT_T) void sift_quota_kernel(SiftArgs a) {
-    if (sift_void(a)) return;
+    if (feat_voided(a)) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = a.ctl->nkp;
     for (int j = blockIdx.x * SIFT_WAVES + wave; j < n; j += gridDim.x * SIFT_WAVES) {
         if (a.flag[j] & 1) continue;
@@ -517,7 +475,7 @@ __global__ __launch_bounds__(SIFT_T) void sift_quota_kernel(SiftArgs a) {
         if (a.nfeatures > 0) {
             const float mine = a.rkey[j];                       // (>= 0; a duplicate's key is -1 and never above)
             for (int i = lane; i < n; i += 64) above += a.rkey[i] > mine;
-            above = sift_wave_sum(above);
+            above = wave_sum(above);
         }
         if (lane == 0 && (a.nfeatures == 0 || above < a.nfeatures)) {
             atomicOr(&a.flag[j], 2);
@@ -531,7 +489,7 @@ __global__ __launch_bounds__(SIFT_T) __attribute__((target("no-packed-fp32-ops")
     __shared__ float s_dst[SIFT_WAVES][SIFT_DESCR_LEN];
     __shared__ float s_scale[SIFT_WAVES], s_thr[SIFT_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool voided = sift_void(a);
+    const bool voided = feat_voided(a);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         a.n_out[0] = voided ? 0 : a.ctl->nout;
         if (voided) atomicOr(a.sticky, (a.ctl->ncand > a.cand_cap ? 1 : 0) | (a.ctl->nkp > a.kp_cap ? 2 : 0));
@@ -549,7 +507,7 @@ __global__ __launch_bounds__(SIFT_T) __attribute__((target("no-packed-fp32-ops")
                 const SiftKey q = sift_key(a.kp, i);
                 less += q.x < me.x || (q.x == me.x && (q.y < me.y || (q.y == me.y && (q.size > me.size || (q.size == me.size && q.ang < me.ang)))));
             }
-        const int pos = sift_wave_sum(less);
+        const int pos = wave_sum(less);
         // the first octave is -1: pt and size halved, the octave byte rebased; then unpackOctave and the descriptor's frame
         const int field = (me.oct & ~255) | ((me.oct - 1) & 255);
         const float x = me.x * 0.5f, y = me.y * 0.5f, size = me.size * 0.5f;
@@ -561,7 +519,7 @@ __global__ __launch_bounds__(SIFT_T) __attribute__((target("no-packed-fp32-ops")
         const SiftOctDev O = a.oc[o];
         const float* G = a.gauss + O.goff + (size_t)layer * ((size_t)O.w * O.h);
         const int ix = (int)rintf(pxf), iy = (int)rintf(pyf);
-        const float rad = ori * K.deg2rad;
+        const float rad = ori * K.atan.deg2rad;
         float cos_t = (float)cos((double)rad), sin_t = (float)sin((double)rad);
         const float bins_per_deg = (float)nb / 360.f;
         const float exp_scale = -1.f / ((float)d * (float)d * 0.5f);
@@ -584,7 +542,7 @@ __global__ __launch_bounds__(SIFT_T) __attribute__((target("no-packed-fp32-ops")
             const float dx = g[1] - g[-1], dy = g[-O.w] - g[O.w];
             const float cc = c_rot * c_rot, rr = r_rot * r_rot;
             const float wgt = sift_exp((cc + rr) * exp_scale);
-            const float so = sift_atan2(K, dy, dx);
+            const float so = fast_atan2_deg(K.atan, dy, dx);
             const float dx2 = dx * dx, dy2 = dy * dy;
             float mag = sqrtf(dx2 + dy2);
             float obin = (so - ori) * bins_per_deg;
@@ -607,16 +565,16 @@ __global__ __launch_bounds__(SIFT_T) __attribute__((target("no-packed-fp32-ops")
                     const int rr2 = r0 + dr, cc2 = c0 + dc;
                     if ((unsigned)rr2 < (unsigned)d && (unsigned)cc2 < (unsigned)d) {
                         unsigned long long* h = &s_acc[wave][(rr2 * d + cc2) * nb];
-                        atomicAdd(&h[o0 & (nb - 1)], sift_fixed(v_o0));
-                        atomicAdd(&h[(o0 + 1) & (nb - 1)], sift_fixed(v_o1));
+                        atomicAdd(&h[o0 & (nb - 1)], to_fixed<SIFT_HIST_SCALE_LOG2, unsigned long long>(v_o0));
+                        atomicAdd(&h[(o0 + 1) & (nb - 1)], to_fixed<SIFT_HIST_SCALE_LOG2, unsigned long long>(v_o1));
                     }
                 }
             }
         }
         __builtin_amdgcn_wave_barrier();
         __threadfence_block();
-        s_dst[wave][lane] = sift_unfixed(s_acc[wave][lane]);
-        s_dst[wave][lane + 64] = sift_unfixed(s_acc[wave][lane + 64]);
+        s_dst[wave][lane] = from_fixed<SIFT_HIST_SCALE_LOG2>(s_acc[wave][lane]);
+        s_dst[wave][lane + 64] = from_fixed<SIFT_HIST_SCALE_LOG2>(s_acc[wave][lane + 64]);
         __builtin_amdgcn_wave_barrier();
         __threadfence_block();
         if (lane == 0) {                                       // the two norms: float32 sums in index order
@@ -743,14 +701,6 @@ int sift_enqueue(sslam_sift* o, const uint8_t* img_dev, int h, int w, int c, flo
     return 0;
 }
 
-int sift_check_call(const char* who, sslam_sift* o, const void* img, int h, int w, int c) {
-    SSLAM_REQUIRE(o != nullptr, "%s: instance is NULL", who);
-    SSLAM_REQUIRE(img != nullptr, "%s: img is NULL", who);
-    char msg[160];
-    if (sift_check_image(w, h, c, o->max_w, o->max_h, msg, sizeof msg)) { sslam::set_error("%s: %s", who, msg); return 2; }
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int sslam_sift_create(sslam_ctx* ctx, int max_w, int max_h, int nfeatures, int n_octave_layers, double contrast_threshold,
@@ -787,28 +737,17 @@ extern "C" int sslam_sift_destroy(sslam_sift* o) {
 }
 
 extern "C" int sslam_sift_capacity(sslam_sift* o, int* rows, int* candidates) {
-    const char* who = "sslam_sift_capacity";
-    SSLAM_REQUIRE(o != nullptr && rows != nullptr, "%s: NULL argument", who);
-    *rows = o->kp_cap;
-    if (candidates) *candidates = o->cand_cap;
-    return 0;
+    return sslam::feat_capacity("sslam_sift_capacity", o, rows, candidates);
 }
 
 extern "C" int sslam_sift_overflow(sslam_sift* o, int* word) {
-    const char* who = "sslam_sift_overflow";
-    SSLAM_REQUIRE(o != nullptr && word != nullptr, "%s: NULL argument", who);
-    SSLAM_HIP_CHECK(hipSetDevice(o->ctx->device));
-    int32_t v = 0;
-    SSLAM_HIP_CHECK(sslam::copy_down(o->ctx->stream, &v, o->sticky, 1));
-    SSLAM_HIP_CHECK(hipStreamSynchronize(o->ctx->stream));
-    *word = v;
-    return 0;
+    return sslam::feat_overflow("sslam_sift_overflow", o, word);
 }
 
 extern "C" int sslam_sift_detect_dev(sslam_sift* o, const uint8_t* img_dev, int h, int w, int c, float* xy_out_dev, float* aux_out_dev,
                                      int32_t* octave_out_dev, float* desc_out_dev, int32_t* n_out_dev) {
     const char* who = "sslam_sift_detect_dev";
-    if (int rc = sift_check_call(who, o, img_dev, h, w, c)) return rc;
+    if (int rc = feat_check_call(who, o, img_dev, h, w, c)) return rc;
     SSLAM_REQUIRE(xy_out_dev && aux_out_dev && octave_out_dev && desc_out_dev && n_out_dev, "%s: an output pointer is NULL", who);
     SSLAM_HIP_CHECK(hipSetDevice(o->ctx->device));
     return sift_enqueue(o, img_dev, h, w, c, xy_out_dev, aux_out_dev, octave_out_dev, desc_out_dev, n_out_dev);
@@ -817,35 +756,13 @@ extern "C" int sslam_sift_detect_dev(sslam_sift* o, const uint8_t* img_dev, int 
 extern "C" int sslam_sift_detect_host(sslam_sift* o, const uint8_t* img, int h, int w, int c, float* xy_out, float* aux_out,
                                       int32_t* octave_out, float* desc_out, int32_t* n_out) {
     const char* who = "sslam_sift_detect_host";
-    if (int rc = sift_check_call(who, o, img, h, w, c)) return rc;
+    if (int rc = feat_check_call(who, o, img, h, w, c)) return rc;
     SSLAM_REQUIRE(xy_out && aux_out && octave_out && desc_out && n_out, "%s: an output pointer is NULL", who);
-    SSLAM_HIP_CHECK(hipSetDevice(o->ctx->device));
-    const size_t bytes = (size_t)h * w * c;
-    char* b;
-    if (int rc = sslam::ctx_scratch(o->ctx, bytes, &b)) return rc;
-    hipStream_t s = o->ctx->stream;
-    SSLAM_HIP_CHECK(hipMemcpyAsync(b, img, bytes, hipMemcpyHostToDevice, s));
-    if (int rc = sift_enqueue(o, (const uint8_t*)b, h, w, c, o->xy, o->aux, o->oct, o->desc, o->n)) return rc;
-    int32_t n = 0;
-    SiftCtl ctl;
-    SSLAM_HIP_CHECK(sslam::copy_down(s, &n, o->n, 1));
-    SSLAM_HIP_CHECK(sslam::copy_down(s, &ctl, o->ctl, 1));
-    SSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    if (ctl.ncand > o->cand_cap || ctl.nkp > o->kp_cap) {
-        sslam::set_error("%s: the frame has %d extrema and %d keypoints before the quota, the instance holds max_candidates %d and "
-                         "max_keypoints %d: the frame is voided, nothing is truncated", who, ctl.ncand, ctl.nkp, o->cand_cap, o->kp_cap);
-        *n_out = 0;
-        return 3;
-    }
-    if (n > 0) {
-        SSLAM_HIP_CHECK(sslam::copy_down(s, xy_out, o->xy, (size_t)n * 2));
-        SSLAM_HIP_CHECK(sslam::copy_down(s, aux_out, o->aux, (size_t)n * 3));
-        SSLAM_HIP_CHECK(sslam::copy_down(s, octave_out, o->oct, (size_t)n));
-        SSLAM_HIP_CHECK(sslam::copy_down(s, desc_out, o->desc, (size_t)n * SIFT_DESCR_LEN));
-        SSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    *n_out = n;
-    return 0;
+    return sslam::feat_detect_host(
+        who, o, img, h, w, c, "extrema",
+        [&](const uint8_t* img_dev) { return sift_enqueue(o, img_dev, h, w, c, o->xy, o->aux, o->oct, o->desc, o->n); },
+        {feat_rows(xy_out, o->xy, 2), feat_rows(aux_out, o->aux, 3), feat_rows(octave_out, o->oct, 1), feat_rows(desc_out, o->desc, SIFT_DESCR_LEN)},
+        n_out);
 }
 
 extern "C" int sslam_sift_octave_info(sslam_sift* o, int octave, int* info8) {

@@ -1,7 +1,7 @@
 // sift_plan.hpp - everything the host decides about a SIFT instance and about one call on it, decided ONCE: the parameter
 // refusals, the octave count, sizes and slab offsets, the per-layer sigmas and float32 tap tables, the integer contrast
 // threshold, the candidate and row capacities, the tile table of the all-octave extrema launch, the fixed-point scale of the
-// two histograms and the float constants (fastAtan2's are ORB's).  Plain C++17 with no HIP include: tests/test_sift_plan.py
+// two histograms and the float constants (fastAtan2's are feat_plan.hpp's).  Plain C++17 with no HIP include: tests/test_sift_plan.py
 // compiles it with the host compiler and compares it with tests/sift_ref.py.  sift_kernels.hip launches from these fields and
 // holds no size arithmetic of its own.  Semantics and what is unconfirmed without cv2: tests/sift_ref.py.
 #pragma once
@@ -12,14 +12,14 @@
 #include <cstdio>
 #include <vector>
 
-#include "orb_plan.hpp"
+#include "feat_plan.hpp"
 
 namespace sslam {
 
 constexpr int SIFT_MAX_OCTAVES = 16;
 constexpr int SIFT_MAX_OCTAVE_LAYERS = 8;
 constexpr int SIFT_MAX_LAYERS = SIFT_MAX_OCTAVE_LAYERS + 3;    // Gaussian layers per octave
-constexpr int SIFT_MAX_SIDE = 16384;
+constexpr int SIFT_MAX_SIDE = FEAT_MAX_SIDE;
 constexpr int SIFT_MAX_FEATURES = 1 << 20;
 constexpr int SIFT_IMG_BORDER = 5;
 constexpr int SIFT_MAX_INTERP_STEPS = 5;
@@ -62,11 +62,10 @@ struct SiftTaps {
 };
 
 struct SiftConsts {
-    float atan_p1, atan_p3, atan_p5, atan_p7, atan_eps, deg2rad, flt_epsilon;
+    FastAtan atan;
+    float flt_epsilon;
     float img_scale, deriv_scale, second_scale, cross_scale;
 };
-
-inline int sift_round(double v) { return (int)std::nearbyint(v); }     // cvRound: half to even
 
 // -> 0, or a non-zero code with the message written
 inline int sift_check_params(const SiftParams& p, int max_w, int max_h, char* msg, size_t n) {
@@ -79,17 +78,9 @@ inline int sift_check_params(const SiftParams& p, int max_w, int max_h, char* ms
     return 0;
 }
 
-// the per-call refusal: an image larger than the instance (never clipped)
-inline int sift_check_image(int w, int h, int c, int max_w, int max_h, char* msg, size_t n) {
-    if (c != 1 && c != 3 && c != 4) { std::snprintf(msg, n, "%d channels (want 1, 3 or 4)", c); return 1; }
-    if (w < 1 || h < 1) { std::snprintf(msg, n, "frame size %dx%d", w, h); return 2; }
-    if (w > max_w || h > max_h) { std::snprintf(msg, n, "frame %dx%d is larger than the instance's %dx%d", w, h, max_w, max_h); return 3; }
-    return 0;
-}
-
 // nOctaves of a w x h input: cvRound(log2(min side of the doubled image) - 2) + 1 (firstOctave -1), none below 1
 inline int sift_n_octaves(int w, int h) {
-    const int n = sift_round(std::log((double)std::min(2 * w, 2 * h)) / std::log(2.0) - 2) + 1;
+    const int n = cv_round(std::log((double)std::min(2 * w, 2 * h)) / std::log(2.0) - 2) + 1;
     return std::min(std::max(n, 0), SIFT_MAX_OCTAVES);
 }
 
@@ -109,7 +100,7 @@ inline SiftPlan sift_plan(const SiftParams& p, int w, int h) {
         P.gauss_floats += plane * (p.nol + 3);
         P.dog_floats += plane * (p.nol + 2);
         const bool interior = ow > 2 * SIFT_IMG_BORDER && oh > 2 * SIFT_IMG_BORDER;     // a side <= 10 yields nothing
-        O.tx = interior ? orb_cdiv(ow, SIFT_TILE_W) : 0; O.ty = interior ? orb_cdiv(oh, SIFT_TILE_H) : 0;
+        O.tx = interior ? feat_cdiv(ow, SIFT_TILE_W) : 0; O.ty = interior ? feat_cdiv(oh, SIFT_TILE_H) : 0;
         O.tile_base = P.ext_tiles;
         P.ext_tiles += O.tx * O.ty;
         P.noct = o + 1;
@@ -130,7 +121,7 @@ inline SiftTaps sift_taps(const SiftParams& p) {
     }
     for (int i = 0; i < p.nol + 3; ++i) {
         const double s = T.sigma[i], s2 = -0.5 / (s * s);
-        const int n = sift_round(s * 8 + 1) | 1;
+        const int n = cv_round(s * 8 + 1) | 1;
         T.n[i] = n; T.off[i] = (int)T.taps.size();
         std::vector<double> t(n);
         double sum = 0;
@@ -142,10 +133,8 @@ inline SiftTaps sift_taps(const SiftParams& p) {
 }
 
 inline SiftConsts sift_consts() {
-    const OrbPlan O = orb_plan(OrbParams{}, 64, 64);           // fastAtan2's polynomial: ORB's
     SiftConsts c{};
-    c.atan_p1 = O.atan_p1; c.atan_p3 = O.atan_p3; c.atan_p5 = O.atan_p5; c.atan_p7 = O.atan_p7; c.atan_eps = O.atan_eps;
-    c.deg2rad = O.deg2rad;
+    c.atan = fast_atan_consts();
     c.flt_epsilon = 1.1920928955078125e-07f;
     c.img_scale = 1.0f / 255.0f;
     c.deriv_scale = c.img_scale * 0.5f; c.second_scale = c.img_scale; c.cross_scale = c.img_scale * 0.25f;

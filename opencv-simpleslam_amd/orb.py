@@ -25,6 +25,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native
+from ._detector import Detector
 
 HARRIS_SCORE = 0           # cv2's values
 FAST_SCORE = 1
@@ -33,8 +34,10 @@ MAX_FEATURES = 1 << 20
 MAX_SIDE = 16384
 
 
-class ORB:
+class ORB(Detector):
     """`cv2.ORB` with `detectAndCompute(image, mask=None)`.  The device instance is made at the first call."""
+    NAME, PREFIX = "ORB", "orb"
+    ROWS = ((2,), np.float32), ((4,), np.float32), ((32,), np.uint8)
 
     def __init__(self, nfeatures=500, scaleFactor=1.2, nlevels=8, edgeThreshold=31, firstLevel=0, WTA_K=2, scoreType=HARRIS_SCORE,
                  patchSize=31, fastThreshold=20, *, pattern=None, max_h=2160, max_w=4096, ctx=None):
@@ -68,67 +71,15 @@ class ORB:
             pattern = np.ascontiguousarray(pattern)
         self.nfeatures, self.scaleFactor, self.nlevels, self.edgeThreshold = nfeatures, float(scaleFactor), nlevels, edgeThreshold
         self.scoreType, self.fastThreshold, self.pattern = int(scoreType), fastThreshold, pattern
-        self.max_h, self.max_w = int(max_h), int(max_w)
-        self.ctx = ctx
-        self.handle = None
-        self.capacity = 0
-        self._out = None                   # the host entry's output arrays, made once ([capacity] rows, pages touched as used)
+        self._setup(max_h, max_w, ctx)
 
-    def _instance(self):
-        if self.handle is None:
-            self.ctx = self.ctx or _native.default_context()
-            h = C.c_void_p()
-            L = _native.lib()
-            _native.check(L.sslam_orb_create(self.ctx.handle, self.max_w, self.max_h, self.nfeatures, float(np.float32(self.scaleFactor)),
-                                             self.nlevels, self.edgeThreshold, self.scoreType, self.fastThreshold,
-                                             _native.ptr(self.pattern), C.byref(h)), "sslam_orb_create")
-            self.handle = h
-            cap = C.c_int(0)
-            _native.check(L.sslam_orb_capacity(h, C.byref(cap)), "sslam_orb_capacity")
-            self.capacity = int(cap.value)
-        return self.handle
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _native.lib().sslam_orb_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _image(self, img, mask):
-        """`img` as the contiguous uint8 [h, w, c] the library takes; anything else is refused, never cast or clipped."""
-        if mask is not None:
-            raise ValueError("ORB.detectAndCompute: a mask is not supported")
-        img = np.asarray(img)
-        if img.dtype != np.uint8:
-            raise TypeError(f"ORB.detectAndCompute: image is {img.dtype}, want uint8")
-        if img.ndim == 2:
-            img = img[:, :, None]
-        if img.ndim != 3 or img.shape[2] not in (1, 3, 4) or img.shape[0] < 1 or img.shape[1] < 1:
-            raise ValueError(f"ORB.detectAndCompute: image must be [h, w] or [h, w, 1 | 3 | 4], got shape {img.shape}")
-        if img.shape[0] > self.max_h or img.shape[1] > self.max_w:
-            raise ValueError(f"ORB.detectAndCompute: image {img.shape[1]}x{img.shape[0]} is larger than the instance's "
-                             f"{self.max_w}x{self.max_h} (max_w x max_h)")
-        return np.ascontiguousarray(img)
+    def _create(self, L, handle_ref):
+        return L.sslam_orb_create(self.ctx.handle, self.max_w, self.max_h, self.nfeatures, float(np.float32(self.scaleFactor)), self.nlevels,
+                                  self.edgeThreshold, self.scoreType, self.fastThreshold, _native.ptr(self.pattern), handle_ref)
 
     def detect_arrays(self, img, mask=None):
         """-> (xy float32 [N,2], aux float32 [N,4] = size, angle, response, octave, desc uint8 [N,32])."""
-        img = self._image(img, mask)
-        h = self._instance()
-        if self._out is None:
-            cap = self.capacity
-            self._out = np.empty((cap, 2), np.float32), np.empty((cap, 4), np.float32), np.empty((cap, 32), np.uint8)
-        xy, aux, desc = self._out
-        n = C.c_int32(0)
-        P = _native.ptr
-        _native.check(_native.lib().sslam_orb_detect_host(h, P(img), img.shape[0], img.shape[1], img.shape[2], P(xy), P(aux), P(desc),
-                                                          C.byref(n)), "sslam_orb_detect_host")
-        k = n.value
-        return xy[:k].copy(), aux[:k].copy(), desc[:k].copy()
+        return self._detect_host(img, mask)
 
     def detectAndCompute(self, image, mask=None):
         """-> (list of KeyPoint with every field set, descriptors uint8 [N, 32]); ([], None) without a keypoint.  KeyPoint is
@@ -140,23 +91,12 @@ class ORB:
         kps = [KeyPoint(x, y, s, a, r, int(o), -1) for (x, y), (s, a, r, o) in zip(xy.tolist(), aux.tolist())]
         return kps, desc
 
-    @property
-    def chain_rows(self) -> int:
-        """The row bound to hand `BFMatcher.match_dev` (M, N) and `epipolar.filter_matches_dev` (n_max) for this instance's
-        device outputs: min(capacity, 65 536), the matcher's limit.  The arrays themselves hold `capacity` rows; the matcher
-        clamps the device count to the bound, so of a frame with more keypoints than that - ties on a large frame, never a
-        quota - only the first 65 536 in output order (the finest levels) take part in the match."""
-        from .bf_matcher import MAX_ROWS
-        self._instance()
-        return min(self.capacity, MAX_ROWS)
-
     def detect_dev(self, img_dev, h: int, w: int, c: int, xy_out_dev, aux_out_dev, desc_out_dev, n_out_dev):
         """Device-resident call: the `*_dev` arguments are device pointers (ints) - the image uint8 [h, w, c], xy float32
         [capacity, 2], aux float32 [capacity, 4], desc uint8 [capacity, 32], the count int32 [1] - and everything stays on the
         device: `desc_out_dev` / `n_out_dev` are what `BFMatcher.match_dev` takes as `q_dev` / `m_dev` (with `chain_rows`, not
         the capacity, as its M), `xy_out_dev` what `epipolar.filter_matches_dev` takes as `xy1_dev`.  Enqueued on the instance's context stream, no synchronisation."""
-        if not (1 <= int(h) <= self.max_h and 1 <= int(w) <= self.max_w):
-            raise ValueError(f"ORB.detect_dev: image {w}x{h} is larger than the instance's {self.max_w}x{self.max_h}")
+        self._check_dev_size(h, w)
         P = _native.ptr
         _native.check(_native.lib().sslam_orb_detect_dev(self._instance(), P(img_dev), int(h), int(w), int(c), P(xy_out_dev),
                                                          P(aux_out_dev), P(desc_out_dev), P(n_out_dev)), "sslam_orb_detect_dev")

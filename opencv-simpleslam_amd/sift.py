@@ -19,11 +19,10 @@ raises `_native.NativeError`; it is never truncated.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _native
+from ._detector import CapacityDetector
 
 MAX_OCTAVE_LAYERS = 8
 MAX_FEATURES = 1 << 20
@@ -31,8 +30,10 @@ MAX_SIDE = 16384
 CV_32F = 5                 # cv2's value
 
 
-class SIFT:
+class SIFT(CapacityDetector):
     """`cv2.SIFT` with `detectAndCompute(image, mask=None)`.  The device instance is made at the first call."""
+    NAME, PREFIX = "SIFT", "sift"
+    ROWS = ((2,), np.float32), ((3,), np.float32), ((), np.int32), ((128,), np.float32)
 
     def __init__(self, nfeatures=0, nOctaveLayers=3, contrastThreshold=0.04, edgeThreshold=10, sigma=1.6, descriptorType=CV_32F,
                  enable_precise_upscale=False, *, max_h=2160, max_w=4096, max_candidates=0, max_keypoints=0, ctx=None):
@@ -57,70 +58,17 @@ class SIFT:
             raise ValueError(f"SIFT_create: max_candidates {max_candidates} / max_keypoints {max_keypoints} is negative (0: the default)")
         self.nfeatures, self.nOctaveLayers = nfeatures, nOctaveLayers
         self.contrastThreshold, self.edgeThreshold, self.sigma = float(contrastThreshold), float(edgeThreshold), float(sigma)
-        self.max_h, self.max_w = int(max_h), int(max_w)
         self.max_candidates, self.max_keypoints = int(max_candidates), int(max_keypoints)
-        self.ctx = ctx
-        self.handle = None
-        self.capacity = 0                  # rows of every output array
-        self.candidate_capacity = 0
-        self._out = None                   # the host entry's output arrays, made once
+        self._setup(max_h, max_w, ctx)
 
-    def _instance(self):
-        if self.handle is None:
-            self.ctx = self.ctx or _native.default_context()
-            h = C.c_void_p()
-            L = _native.lib()
-            _native.check(L.sslam_sift_create(self.ctx.handle, self.max_w, self.max_h, self.nfeatures, self.nOctaveLayers,
-                                              self.contrastThreshold, self.edgeThreshold, self.sigma, self.max_candidates,
-                                              self.max_keypoints, C.byref(h)), "sslam_sift_create")
-            self.handle = h
-            rows, cand = C.c_int(0), C.c_int(0)
-            _native.check(L.sslam_sift_capacity(h, C.byref(rows), C.byref(cand)), "sslam_sift_capacity")
-            self.capacity, self.candidate_capacity = int(rows.value), int(cand.value)
-        return self.handle
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _native.lib().sslam_sift_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _image(self, img, mask):
-        """`img` as the contiguous uint8 [h, w, c] the library takes; anything else is refused, never cast or clipped."""
-        if mask is not None:
-            raise ValueError("SIFT.detectAndCompute: a mask is not supported")
-        img = np.asarray(img)
-        if img.dtype != np.uint8:
-            raise TypeError(f"SIFT.detectAndCompute: image is {img.dtype}, want uint8")
-        if img.ndim == 2:
-            img = img[:, :, None]
-        if img.ndim != 3 or img.shape[2] not in (1, 3, 4) or img.shape[0] < 1 or img.shape[1] < 1:
-            raise ValueError(f"SIFT.detectAndCompute: image must be [h, w] or [h, w, 1 | 3 | 4], got shape {img.shape}")
-        if img.shape[0] > self.max_h or img.shape[1] > self.max_w:
-            raise ValueError(f"SIFT.detectAndCompute: image {img.shape[1]}x{img.shape[0]} is larger than the instance's "
-                             f"{self.max_w}x{self.max_h} (max_w x max_h)")
-        return np.ascontiguousarray(img)
+    def _create(self, L, handle_ref):
+        return L.sslam_sift_create(self.ctx.handle, self.max_w, self.max_h, self.nfeatures, self.nOctaveLayers,
+                                   self.contrastThreshold, self.edgeThreshold, self.sigma, self.max_candidates,
+                                   self.max_keypoints, handle_ref)
 
     def detect_arrays(self, img, mask=None):
         """-> (xy float32 [N,2], aux float32 [N,3] = size, angle, response, octave int32 [N], desc float32 [N,128])."""
-        img = self._image(img, mask)
-        h = self._instance()
-        if self._out is None:
-            cap = self.capacity
-            self._out = (np.empty((cap, 2), np.float32), np.empty((cap, 3), np.float32), np.empty(cap, np.int32),
-                         np.empty((cap, 128), np.float32))
-        xy, aux, octave, desc = self._out
-        n = C.c_int32(0)
-        P = _native.ptr
-        _native.check(_native.lib().sslam_sift_detect_host(h, P(img), img.shape[0], img.shape[1], img.shape[2], P(xy), P(aux), P(octave),
-                                                           P(desc), C.byref(n)), "sslam_sift_detect_host")
-        k = n.value
-        return xy[:k].copy(), aux[:k].copy(), octave[:k].copy(), desc[:k].copy()
+        return self._detect_host(img, mask)
 
     def detectAndCompute(self, image, mask=None):
         """-> (list of KeyPoint with every field set, descriptors float32 [N, 128]); ([], None) without a keypoint.  KeyPoint is
@@ -132,33 +80,17 @@ class SIFT:
         kps = [KeyPoint(x, y, s, a, r, o, -1) for (x, y), (s, a, r), o in zip(xy.tolist(), aux.tolist(), octave.tolist())]
         return kps, desc
 
-    @property
-    def chain_rows(self) -> int:
-        """The row bound to hand `BFMatcher.match_dev` (M, N) and `epipolar.filter_matches_dev` (n_max) for this instance's
-        device outputs: min(capacity, 65 536), the matcher's limit; the arrays themselves hold `capacity` rows."""
-        from .bf_matcher import MAX_ROWS
-        self._instance()
-        return min(self.capacity, MAX_ROWS)
-
     def detect_dev(self, img_dev, h: int, w: int, c: int, xy_out_dev, aux_out_dev, octave_out_dev, desc_out_dev, n_out_dev):
         """Device-resident call: the `*_dev` arguments are device pointers (ints) - the image uint8 [h, w, c], xy float32
         [capacity, 2], aux float32 [capacity, 3], octave int32 [capacity], desc float32 [capacity, 128], the count int32 [1] -
         and everything stays on the device: `desc_out_dev` / `n_out_dev` are what `BFMatcher.match_dev` takes as `q_dev` /
         `m_dev` (NORM_L2, D = 128, `chain_rows` as its M), `xy_out_dev` what `epipolar.filter_matches_dev` takes as `xy1_dev`.
         Enqueued on the instance's context stream, no synchronisation; a voided frame writes the count 0 and sets `overflow()`."""
-        if not (1 <= int(h) <= self.max_h and 1 <= int(w) <= self.max_w):
-            raise ValueError(f"SIFT.detect_dev: image {w}x{h} is larger than the instance's {self.max_w}x{self.max_h}")
+        self._check_dev_size(h, w)
         P = _native.ptr
         _native.check(_native.lib().sslam_sift_detect_dev(self._instance(), P(img_dev), int(h), int(w), int(c), P(xy_out_dev),
                                                           P(aux_out_dev), P(octave_out_dev), P(desc_out_dev), P(n_out_dev)),
                       "sslam_sift_detect_dev")
-
-    def overflow(self) -> int:
-        """The sticky word: bit 0 - a frame had more extrema than `max_candidates`, bit 1 - more keypoints than
-        `max_keypoints`; such a frame was voided.  Synchronises the stream."""
-        v = C.c_int(0)
-        _native.check(_native.lib().sslam_sift_overflow(self._instance(), C.byref(v)), "sslam_sift_overflow")
-        return int(v.value)
 
     # test hooks (include/sslam_hip.h: sslam_sift_octave_info, sslam_sift_stage_read)
     def octave_info(self, octave: int):

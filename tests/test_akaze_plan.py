@@ -52,7 +52,7 @@ extern "C" int akz_fed_cycle_shim(double T, int ordered, float* tau, int cap) {
 extern "C" int akz_taps_shim(double sigma, float* taps) { const std::vector<float> t = akz_gauss_taps(sigma); for (size_t i = 0; i < t.size(); ++i) taps[i] = t[i]; return (int)t.size(); }
 extern "C" void akz_consts_shim(float* f, int* c, float* g) {
     const AkzConsts k = akz_consts();
-    const float v[] = {k.atan_p1, k.atan_p3, k.atan_p5, k.atan_p7, k.atan_eps, k.deg2rad, k.win_step, k.pi3, k.two_pi, k.five_pi3, k.img_div, k.kfallback, k.koctave};
+    const float v[] = {k.atan.p1, k.atan.p3, k.atan.p5, k.atan.p7, k.atan.eps, k.atan.deg2rad, k.win_step, k.pi3, k.two_pi, k.five_pi3, k.img_div, k.kfallback, k.koctave};
     for (int i = 0; i < 13; ++i) f[i] = v[i];
     const int u[] = {AKZ_DESCRIPTOR_MLDB, AKZ_DIFF_PM_G2, AKZ_MAX_OCTAVES, AKZ_MAX_SUBLEVELS, AKZ_MAX_LEVELS, AKZ_MIN_OCTAVE_W, AKZ_MIN_OCTAVE_H, AKZ_DESC_BYTES,
                      AKZ_DESC_BITS, AKZ_NBINS, AKZ_WG_PIXELS, AKZ_WG_T, AKZ_WG_PER_THREAD, AKZ_FIXED_LOG2, AKZ_N_WINDOWS, AKZ_ORI_SAMPLES};
@@ -64,7 +64,7 @@ extern "C" int akz_params_shim(int dt, int ds, int dc, double thr, int noct, int
     p.diffusivity = diff; p.max_points = maxp;
     return akz_check_params(p, max_w, max_h, msg, (size_t)n);
 }
-extern "C" int akz_image_shim(int w, int h, int c, int max_w, int max_h, char* msg, int n) { return akz_check_image(w, h, c, max_w, max_h, msg, (size_t)n); }
+extern "C" int akz_image_shim(int w, int h, int c, int max_w, int max_h, char* msg, int n) { return feat_check_image(w, h, c, max_w, max_h, msg, (size_t)n); }
 extern "C" long long akz_capacity_shim(int maxp, int max_w, int max_h, int co, int ko, int* cand, int* rows) {
     const AkzParams p = params(4, 4, 0.001, maxp);
     akz_capacities(p, max_w, max_h, co, ko, cand, rows);

@@ -17,6 +17,7 @@ LEVEL_INTS = ("w", "h", "stride", "rows", "active", "quota", "cut1_n", "fast_tx"
               "cand_cap")
 PLAN_INTS = ("w", "h", "nlevels", "border", "nactive", "fast_tiles", "blur_tiles")
 PLAN_FLOATS = ("harris_k", "harris_scale4", "atan_p1", "atan_p3", "atan_p5", "atan_p7", "atan_eps", "deg2rad", "patch_size")
+PLAN_FLOAT_FIELDS = ("harris_k", "harris_scale4", "atan.p1", "atan.p3", "atan.p5", "atan.p7", "atan.eps", "atan.deg2rad", "patch_size")   # in OrbPlan
 NL, NP, NF = len(LEVEL_INTS), len(PLAN_INTS), len(PLAN_FLOATS)
 
 SHIM = r"""
@@ -47,7 +48,7 @@ extern "C" void orb_plan_shim(int nfeatures, double sf, int nlevels, int edge, i
 extern "C" int orb_params_shim(int nfeatures, double sf, int nlevels, int edge, int score, int fast, int max_w, int max_h, char* msg, int n) {
     return orb_check_params(params(nfeatures, sf, nlevels, edge, score, fast), max_w, max_h, msg, (size_t)n);
 }
-extern "C" int orb_image_shim(int w, int h, int c, int max_w, int max_h, char* msg, int n) { return orb_check_image(w, h, c, max_w, max_h, msg, (size_t)n); }
+extern "C" int orb_image_shim(int w, int h, int c, int max_w, int max_h, char* msg, int n) { return feat_check_image(w, h, c, max_w, max_h, msg, (size_t)n); }
 extern "C" int orb_pattern_check_shim(const signed char* p, char* msg, int n) { return orb_check_pattern((const int8_t*)p, msg, (size_t)n); }
 extern "C" void orb_pattern_shim(signed char* out) { orb_default_pattern((int8_t*)out); }
 extern "C" long long orb_capacity_shim(int nfeatures, double sf, int nlevels, int edge, int max_w, int max_h) {
@@ -57,7 +58,7 @@ extern "C" void orb_constants_shim(int* o) {
     const int v[] = {ORB_MAX_LEVELS, ORB_MAX_SIDE, ORB_MAX_FEATURES, ORB_PATCH, ORB_HALF, ORB_REACH, ORB_PATTERN_POINTS, ORB_TILE_W, ORB_TILE_H, ORB_FAST_W, ORB_FAST_H};
     for (size_t i = 0; i < sizeof(v) / sizeof(v[0]); ++i) o[i] = v[i];
 }
-""" % (", ".join("P." + n for n in PLAN_INTS), ", ".join("P." + n for n in PLAN_FLOATS), ", ".join("L." + n for n in LEVEL_INTS), NL)
+""" % (", ".join("P." + n for n in PLAN_INTS), ", ".join("P." + n for n in PLAN_FLOAT_FIELDS), ", ".join("L." + n for n in LEVEL_INTS), NL)
 
 
 @pytest.fixture(scope="module")

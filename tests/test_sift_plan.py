@@ -40,7 +40,7 @@ extern "C" int sift_taps_shim(int nol, double sigma, int* n, int* off, double* s
 }
 extern "C" void sift_consts_shim(float* f, int* c) {
     const SiftConsts k = sift_consts();
-    const float v[] = {k.atan_p1, k.atan_p3, k.atan_p5, k.atan_p7, k.atan_eps, k.deg2rad, k.flt_epsilon, k.img_scale, k.deriv_scale, k.second_scale, k.cross_scale};
+    const float v[] = {k.atan.p1, k.atan.p3, k.atan.p5, k.atan.p7, k.atan.eps, k.atan.deg2rad, k.flt_epsilon, k.img_scale, k.deriv_scale, k.second_scale, k.cross_scale};
     for (int i = 0; i < 11; ++i) f[i] = v[i];
     const int u[] = {SIFT_MAX_OCTAVES, SIFT_MAX_OCTAVE_LAYERS, SIFT_MAX_SIDE, SIFT_MAX_FEATURES, SIFT_IMG_BORDER, SIFT_MAX_INTERP_STEPS, SIFT_ORI_BINS,
                      SIFT_DESCR_WIDTH, SIFT_DESCR_BINS, SIFT_DESCR_LEN, SIFT_TILE_W, SIFT_TILE_H, SIFT_HIST_SCALE_LOG2};
@@ -49,7 +49,7 @@ extern "C" void sift_consts_shim(float* f, int* c) {
 extern "C" int sift_params_shim(int nfeatures, int nol, double contrast, double edge, double sigma, int max_w, int max_h, char* msg, int n) {
     return sift_check_params(params(nfeatures, nol, contrast, edge, sigma), max_w, max_h, msg, (size_t)n);
 }
-extern "C" int sift_image_shim(int w, int h, int c, int max_w, int max_h, char* msg, int n) { return sift_check_image(w, h, c, max_w, max_h, msg, (size_t)n); }
+extern "C" int sift_image_shim(int w, int h, int c, int max_w, int max_h, char* msg, int n) { return feat_check_image(w, h, c, max_w, max_h, msg, (size_t)n); }
 extern "C" long long sift_capacity_shim(int nfeatures, int nol, int max_w, int max_h, int co, int ko, int* cand, int* rows) {
     const SiftParams p = params(nfeatures, nol, 0.04, 10, 1.6);
     sift_capacities(p, max_w, max_h, co, ko, cand, rows);
