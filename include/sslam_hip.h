@@ -733,6 +733,49 @@ int sslam_thumb_resize_host(sslam_thumb* t, const uint8_t* src, int Hs, int Ws, 
  * 4 coefficients int16 [blocks][64], zigzag order, blocks in scan order; 5 bit offsets uint32 [blocks] */
 int sslam_thumb_stage_read(sslam_thumb* t, int which, void* dst);
 
+/* ------------------------------------------------------- semi-global stereo
+ * Replaces `cv2.StereoSGBM_create(...).compute(left, right)` of the reference's stereo prototype
+ * (refrences/sfm_lightglue_aliked.py:109-121, :357-361) and the lookup + `cv2.triangulatePoints(Proj, Proj_r, ...)` behind it
+ * (:363-396).  8-bit input, MODE_SGBM (single pass, five paths), no speckle filter; integers only, defined stage by stage in
+ * tests/stereo_ref.py, which the device equals bit for bit.  Parity with cv2 itself is unpinned (the restatement's UNCONFIRMED).
+ * Normalised: P1 <= 0 -> 2; P2 -> max(P2 > 0 ? P2 : 5, P1 + 1); disp12MaxDiff <= 0 -> 1 (the left-right check always runs);
+ * uniquenessRatio < 0 -> 10; ftzero = max(preFilterCap, 15) | 1.  The result is int16 [H][W] in sixteenths of a pixel; columns
+ * below minDisparity + numDisparities and rejected pixels hold (minDisparity - 1) * 16, as does the whole image when
+ * W <= minDisparity + numDisparities (not an error).
+ * Refused with a message naming the value, before any device call: mode != 0 (MODE_SGBM), speckleWindowSize > 0, minDisparity < 0,
+ * numDisparities not a multiple of 16 in 16..256, blockSize even or outside 1..11, preFilterCap outside 0..63,
+ * uniquenessRatio > 100, a side outside 1..16384, a parameter set whose largest block cost
+ * (blockSize^2 * ((2 ftzero >> 2) + 63)) + P2 exceeds 32767, a workspace above 4 GiB. */
+typedef struct sslam_sgbm sslam_sgbm;
+int sslam_sgbm_create(sslam_ctx* ctx, int max_w, int max_h, int minDisparity, int numDisparities, int blockSize, int P1, int P2,
+                      int disp12MaxDiff, int preFilterCap, int uniquenessRatio, int speckleWindowSize, int speckleRange, int mode,
+                      sslam_sgbm** out);
+int sslam_sgbm_destroy(sslam_sgbm* g);
+/* left, right uint8 [H][W][channels] (host), channels 1, 3 or 4: 3 and 4 (B G R [A]) are converted to grey first - the
+ * prototype's call order, NOT cv2's per-channel cost.  disp int16 [H][W] (host). */
+int sslam_sgbm_compute_host(sslam_sgbm* g, const uint8_t* left, const uint8_t* right, int H, int W, int channels, int16_t* disp);
+/* device pointers; enqueue only */
+int sslam_sgbm_compute_dev(sslam_sgbm* g, const uint8_t* left_dev, const uint8_t* right_dev, int H, int W, int channels,
+                           int16_t* disp_dev);
+/* for tests, of the LAST compute (synchronises), W1 = max(W - minDisparity - numDisparities, 0).  which: 0 / 1 the prefiltered
+ * plane of the left / right image uint8 [H][W]; 2 C, 3 S int16 [H][W1][D]; 4 the disparity before the left-right check, 5 the
+ * right view's integer disparity, 6 the checked disparity before the median, each int16 [H][W] */
+int sslam_sgbm_stage_read(sslam_sgbm* g, int which, void* dst);
+/* The keypoint lift, a keypoint per thread.  xy float32 [n][2]; disp int16 [H][W] (a compute's output).  d = disp[int(y)][int(x)]
+ * / 16 in float32; mask = min_disp < d < max_disp, clear for a keypoint outside the image (the prototype would raise or wrap:
+ * a stated departure); xy_right = (x - d, y); X = v[:3] / v[3] of the DLT null vector of (P_left, P_right) as
+ * sslam_triangulate_2view computes it, |v[3]| <= 1e-12 clears the mask, X is NaN where the mask is clear.  xy_right_in != NULL:
+ * the right pixels are given (disp is not read, d = x - x_right, every keypoint is a candidate).  P_left12 / P_right12 are host
+ * 3 x 4 row-major, both NULL: no triangulation (X_out must be NULL).  d_out, xy_right_out, X_out may be NULL.
+ * _dev: device pointers, enqueue only; n_dev (may be NULL) is a device-resident count clamped to [0, n_max], nothing is written
+ * beyond it. */
+int sslam_stereo_lift_host(sslam_ctx* ctx, int n, const float* xy, const float* xy_right_in, const int16_t* disp, int H, int W,
+                           const double* P_left12, const double* P_right12, double min_disp, double max_disp, float* d_out,
+                           float* xy_right_out, double* X_out, uint8_t* mask_out);
+int sslam_stereo_lift_dev(sslam_ctx* ctx, int n_max, const int32_t* n_dev, const float* xy_dev, const float* xy_right_in_dev,
+                          const int16_t* disp_dev, int H, int W, const double* P_left12, const double* P_right12, double min_disp,
+                          double max_disp, float* d_out_dev, float* xy_right_out_dev, double* X_out_dev, uint8_t* mask_out_dev);
+
 /* ------------------------------------------------------------------ ALIKED
  * Replaces `ALIKED(max_num_keypoints=...).eval().to(device)` at
  * slam/core/features_utils.py:25 and `_bgr_to_tensor` + `detector.extract` +

@@ -135,6 +135,13 @@ def _signatures():
         "sslam_thumb_encode_dev": (i32, [vp, vp, i32, i32, i32, vp, vp]),
         "sslam_thumb_resize_host": (i32, [vp, vp, i32, i32, i32, vp]),
         "sslam_thumb_stage_read": (i32, [vp, i32, vp]),
+        "sslam_sgbm_create": (i32, [vp] + [i32] * 13 + [c_void_pp]),
+        "sslam_sgbm_destroy": (i32, [vp]),
+        "sslam_sgbm_compute_host": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+        "sslam_sgbm_compute_dev": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+        "sslam_sgbm_stage_read": (i32, [vp, i32, vp]),
+        "sslam_stereo_lift_host": (i32, [vp, i32, vp, vp, vp, i32, i32, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp]),
+        "sslam_stereo_lift_dev": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp]),
         "sslam_aliked_create": (i32, [vp, vp, sz, i32, i32, i32, c_void_pp]),
         "sslam_aliked_create_batched": (i32, [vp, vp, sz, i32, i32, i32, i32, c_void_pp]),
         "sslam_aliked_extract_batch_dev": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
