@@ -17,7 +17,9 @@ constexpr int B1_SW = 30;             // al_block1_rows_kernel: output pixels pe
 constexpr int B2_SW = 30;             // al_block2_rows_kernel: output pixels per strip
 constexpr int DCN3_CS = 1;            // workgroups per pixel tile of the 1/8 deformable layers ...
 constexpr int DCN4_CS = 4;            // ... and of the 1/32 ones (output channels split: 10 tiles per frame there)
-constexpr int AGG_PRE = 13;           // al_agg_pre_kernel: planes per level (8 projections + S, H, V, D1, D2)
+constexpr int AGG_PRE = 13;           // pre-aggregation planes per level (8 projections + S, H, V, D1, D2)
+constexpr int L2_TW = 32, L2_TH = 8;  // al_level2_kernel: interior tile of 1/2-level pixels (whole 4 x 4 pooling cells)
+constexpr int LS_TW = 16, LS_TH = 4;  // al_level_small_kernel: interior tile of 1/8- and 1/32-level pixels
 constexpr int ST_W = 32, ST_H = 8;    // al_score_tail_kernel: output tile
 constexpr int PRE_LDS_MAX = 48 * 1024;  // al_preprocess_kernel: most LDS bytes a tile may take (three workgroups per CU at least)
 constexpr int NHALO = 10;             // dependency radius of simple_nms: 2 + 4 + 4
@@ -68,6 +70,10 @@ struct ALPlan {
     // horizontally blurred source span they read in LDS: at most pre_cols columns x pre_rows rows per channel, beside the raw
     // bytes of those rows (pre_raw bytes per row) and the 256 floats of b / 255
     int pre_tw, pre_th, pre_gx, pre_gy, pre_cols, pre_rows, pre_raw, pre_lds;
+    // the fused gate + pre-aggregation kernels: L2_TW x L2_TH tiles of the 1/2 level (al_level2_kernel, which also pools into
+    // block3), LS_TW x LS_TH tiles of the two small levels in one launch (lvl3_n workgroups of the 1/8 level, then lvl4_n)
+    int lvl2_gx, lvl2_gy;
+    int lvl3_gx, lvl3_n, lvl4_gx, lvl4_n, lvl34_n;
 };
 
 inline ALPlan al_plan(int H, int W, int C, int F) {
@@ -124,6 +130,10 @@ inline ALPlan al_plan(int H, int W, int C, int F) {
     p.sy2 = step(Hp, 2); p.sx2 = step(Wp, 2); p.sy8 = step(Hp, 8); p.sx8 = step(Wp, 8);
     p.sy32 = step(Hp, 32); p.sx32 = step(Wp, 32);
     p.agg_pre_gx = al_cdiv(p.HW2 + p.HW3 + p.HW4, 256);
+    p.lvl2_gx = al_cdiv(p.W2, L2_TW); p.lvl2_gy = al_cdiv(p.H2, L2_TH);
+    p.lvl3_gx = al_cdiv(p.W3, LS_TW); p.lvl3_n = p.lvl3_gx * al_cdiv(p.H3, LS_TH);
+    p.lvl4_gx = al_cdiv(p.W4, LS_TW); p.lvl4_n = p.lvl4_gx * al_cdiv(p.H4, LS_TH);
+    p.lvl34_n = p.lvl3_n + p.lvl4_n;
     p.tail_gx = al_cdiv(Wp, ST_W); p.tail_gy = al_cdiv(Hp, ST_H);
     // DKD on the un-padded map
     p.nbx = al_cdiv(d.w, NW_OW); p.nby = al_cdiv(d.h, NW_OH); p.n_tiles = p.nbx * p.nby;

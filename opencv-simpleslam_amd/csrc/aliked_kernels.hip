@@ -978,71 +978,8 @@ __global__ __launch_bounds__(256) void al_dcn_h_kernel(const float* __restrict__
 }
 
 
-// conv weights [ci][tap][co] -> [co][tap*CIN + ci]; 1x1 weights [ci][co] -> [co][ci] (taps = 1)
-
-// 1x1 conv (no bias) + SELU: one thread per pixel produces all 32 outputs (inputs read once,
-// weights [ci][32] as wave-uniform scalar loads).  r04: the channel loop is unrolled with every input of the pixel loaded up
-// front (rolled, each of its 32 trips waited for its own load: 32 serial memory latencies per thread), and the channel-last
-// copy leaves through LDS as whole 128-byte lines per 8 lanes (direct, every lane wrote 16-byte pieces of its own line).
-template <int CIN>
-__global__ __launch_bounds__(256) void al_gate_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                      int HW, const float* __restrict__ w /*[ci][32]*/,
-                                                      float* __restrict__ out_cl /*[HW][32]*/, size_t fs) {
-    __shared__ float cl[256 * 33];
-    const int p0 = blockIdx.x * blockDim.x, p = p0 + threadIdx.x, pc = min(p, HW - 1);
-    in = fsh(in, blockIdx.y, fs); out = fsh(out, blockIdx.y, fs); out_cl = fsh(out_cl, blockIdx.y, fs);
-    float v[CIN];
-#pragma unroll
-    for (int ci = 0; ci < CIN; ++ci) v[ci] = in[(size_t)ci * HW + pc];
-    float acc[32];
-#pragma unroll
-    for (int o = 0; o < 32; ++o) acc[o] = 0.0f;
-#pragma unroll
-    for (int ci = 0; ci < CIN; ++ci) {
-        const float* wp = w + ci * 32;
-#pragma unroll
-        for (int o = 0; o < 32; ++o) acc[o] = fmaf(v[ci], wp[o], acc[o]);
-    }
-#pragma unroll
-    for (int o = 0; o < 32; ++o) { acc[o] = selu(acc[o]); cl[threadIdx.x * 33 + o] = acc[o]; }
-    if (p < HW) {
-#pragma unroll
-        for (int o = 0; o < 32; ++o) out[(size_t)o * HW + p] = acc[o];
-    }
-    __syncthreads();
-    const int npx = min(256, HW - p0);
-    float* dst = out_cl + (size_t)p0 * 32;
-    for (int i = threadIdx.x; i < npx * 8; i += 256) {
-        const int q = i >> 3, c4 = (i & 7) * 4;
-        *reinterpret_cast<float4*>(dst + (size_t)q * 32 + c4) = make_float4(cl[q * 33 + c4], cl[q * 33 + c4 + 1], cl[q * 33 + c4 + 2], cl[q * 33 + c4 + 3]);
-    }
-}
-
-// small-map variant (1/8, 1/32 resolution): one thread per (co, pixel), more parallelism.  r06: both small levels in ONE launch
-// (a launch of a few workgroups is ~5 us of a single frame's dependent chain): the first `blocks_a` workgroups gate level a,
-// the rest level b - each thread's arithmetic is what its own launch did.
-struct GateSmall { const float* in; float* out; int CIN; int HW; const float* w; float* out_cl; };
-__global__ void al_gate_small_kernel(GateSmall a, GateSmall b, int blocks_a, size_t fs) {
-    const bool second = (int)blockIdx.x >= blocks_a;
-    const GateSmall& q = second ? b : a;
-    const int i = ((int)blockIdx.x - (second ? blocks_a : 0)) * blockDim.x + threadIdx.x;
-    const int CIN = q.CIN, HW = q.HW;
-    if (i >= 32 * HW) return;
-    const float* __restrict__ in = fsh(q.in, blockIdx.y, fs);
-    float* __restrict__ out = fsh(q.out, blockIdx.y, fs);
-    float* __restrict__ out_cl = fsh0(q.out_cl, blockIdx.y, fs);
-    const float* __restrict__ w = q.w;           /*[ci][32]*/
-    const int co = i / HW, p = i % HW;
-    float a0 = 0.0f, a1 = 0.0f;
-#pragma unroll 8                 // 16 loads in flight per thread: the loop is pure load latency otherwise
-    for (int ci = 0; ci < CIN; ci += 2) {
-        a0 = fmaf(in[(size_t)ci * HW + p], w[ci * 32 + co], a0);
-        a1 = fmaf(in[(size_t)(ci + 1) * HW + p], w[(ci + 1) * 32 + co], a1);
-    }
-    const float v = selu(a0 + a1);
-    out[i] = v;
-    out_cl[(size_t)p * 32 + co] = v;
-}
+// (the gates g_i = selu(conv1x1(x_i)) of the three pyramid levels are formed by the kernels that also reduce them to the
+//  pre-aggregation planes: al_level2_kernel / al_level_small_kernel in section 3)
 
 // ------------------------------------------------------------------------ //
 //  3. feature aggregation.  F(p) = [ selu(W1 x1(p)) | up2(g2)(p) | up8(g3)(p) | up32(g4)(p) ]
@@ -1050,8 +987,8 @@ __global__ void al_gate_small_kernel(GateSmall a, GateSmall b, int blocks_a, siz
 //     score-head layer s8 = selu(Ws0 F) and 1/||F|| without storing F.
 // ------------------------------------------------------------------------ //
 struct Pyr {
-    const float* x1; const float* g2; const float* g3; const float* g4;
-    const float* w1;      // conv1 [16][32]
+    const float* x1;
+    const float* w1t;     // conv1 transposed, [32][16]: a channel's 16 weights are one 64-byte scalar load (r35)
     int Hp, Wp;
     float* g1cl;          // selu(W1 x1) channel-last [Hp][Wp][32], written by the aggregate kernel
     // align_corners=True source steps (ih - 1) / (Hp - 1) of the three upsampled levels (host-computed:
@@ -1061,12 +998,12 @@ struct Pyr {
     // tap of all 32 channels is then ONE 128-byte line instead of 32 lines of 32 planes
     const float *g2cl, *g3cl, *g4cl;
     // r04: what the aggregate kernel needs of an upsampled level, formed ONCE at the level's own resolution
-    // (al_agg_pre_kernel): [AGG_PRE][pixels] planar per level - see there
+    // (al_level2_kernel / al_level_small_kernel): [AGG_PRE][pixels] planar per level - see there
     const float *pre2, *pre3, *pre4;
 };
 
-__device__ __forceinline__ Pyr pyr_at(Pyr P, int f, size_t fs) {      // the pyramid of frame f (weights w1 shared)
-    P.x1 = fsh(P.x1, f, fs); P.g2 = fsh(P.g2, f, fs); P.g3 = fsh(P.g3, f, fs); P.g4 = fsh(P.g4, f, fs);
+__device__ __forceinline__ Pyr pyr_at(Pyr P, int f, size_t fs) {      // the pyramid of frame f (weights w1t shared)
+    P.x1 = fsh(P.x1, f, fs);
     P.g1cl = fsh(P.g1cl, f, fs); P.g2cl = fsh(P.g2cl, f, fs); P.g3cl = fsh(P.g3cl, f, fs); P.g4cl = fsh(P.g4cl, f, fs);
     P.pre2 = fsh(P.pre2, f, fs); P.pre3 = fsh(P.pre3, f, fs); P.pre4 = fsh(P.pre4, f, fs);
     return P;
@@ -1101,36 +1038,24 @@ __device__ __forceinline__ float up_eval(const float* __restrict__ p, const UpTa
 //     S[p] = <g[p], g[p]>, H[p] = <g[p], g[p + x]>, V[p] = <g[p], g[p + y]>, D1[p] = <g[p], g[p + x + y]>,
 //     D2[p] = <g[p + x], g[p + y]>                                          (5 maps)
 //     sum_c up(g_c)^2 = sum_{t, t'} w_t w_t' <g[t], g[t']> over the four taps = a quadratic form in S, H, V, D1, D2
-// (neighbours clamped at the border, where their tap weight is exactly zero).  One thread per level pixel, all three levels
-// of a frame in one launch; reads the planar levels.
-constexpr int PRE_UNROLL = 32;        // all 128 loads of a thread in flight at once: 5.4 us per frame (rounds of 8 / 16 channels: 11.3 / 18.5 - a memory latency per round)
-__global__ __launch_bounds__(256) void al_agg_pre_kernel(const float* __restrict__ g2cl /* planar [32][pixels] */, const float* __restrict__ g3cl,
-                                                         const float* __restrict__ g4cl, const float* __restrict__ ws0 /*[128][8]*/,
-                                                         float* __restrict__ pre2, float* __restrict__ pre3, float* __restrict__ pre4,
-                                                         int Hp, int Wp, size_t fs) {
-    // (xcd_band() here halves this kernel's fetch - 23.3 -> 11.2 MB per frame, its threads read their pixel's right and lower
-    //  neighbours - and costs it 20 % of its time, 6.1 -> 7.4 us per frame: eight far-apart streams per plane instead of one; not used)
-    const int f = blockIdx.y;
-    const int n2 = (Hp / 2) * (Wp / 2), n3 = (Hp / 8) * (Wp / 8), n4 = (Hp / 32) * (Wp / 32);
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const float* g; float* pre; int S, lvl;
-    if (i < n2) { g = g2cl; pre = pre2; S = 2; lvl = 1; }
-    else if (i < n2 + n3) { i -= n2; g = g3cl; pre = pre3; S = 8; lvl = 2; }
-    else if (i < n2 + n3 + n4) { i -= n2 + n3; g = g4cl; pre = pre4; S = 32; lvl = 3; }
-    else return;
-    g = fsh(g, f, fs); pre = fsh(pre, f, fs);
-    const int ih = Hp / S, iw = Wp / S, n = ih * iw;
-    const int y = i / iw, x = i % iw;
-    const int xr = x + (x < iw - 1), yd = y + (y < ih - 1);
-    const int ia = y * iw + x, ib = y * iw + xr, ic = yd * iw + x, id = yd * iw + xr;
+// (neighbours clamped at the border, where their tap weight is exactly zero).
+//
+// r35: the planes are formed by the kernel that gates the level, from the gated values it holds in LDS for the channel-last
+// store.  (Before, the gate kernels also wrote the level planar - 10.5 MB per frame at 1/2 - for a kernel of its own,
+// al_agg_pre, that read every pixel and three neighbours back: 23.3 MB fetched per frame.)  A workgroup owns a tile of level
+// pixels and gates the one-pixel right and lower halo as well; halo coordinates are CLAMPED to the map, so the LDS copy of a
+// border pixel's "neighbour" is the pixel itself, as xr = x + (x < iw - 1) / yd = y + (y < ih - 1) picked it.  Every value is
+// the two-kernel form's bit for bit: the gate sums keep their chains (below), the planes al_agg_pre's expressions - c ascending,
+// one fmaf chain per plane.  The planar g2..g4 buffers stay carved; sslam_aliked_debug_read fills them on request.
+//
+// the 13 planes of one level pixel from the LDS tile ([pixel][33] floats, `row` pixels per tile row): pixel at `ia`
+__device__ __forceinline__ void pre_planes_lds(const float* __restrict__ cl, int ia, int row, const float* __restrict__ w /*[32][8]: the level's rows of ws0*/,
+                                               float* __restrict__ pre, int n, int i) {
+    const int ib = ia + 33, ic = ia + row * 33, id = ic + 33;
     float pr[8] = {}, ss = 0.0f, hh = 0.0f, vv = 0.0f, d1 = 0.0f, d2 = 0.0f;
-    const float* w = ws0 + lvl * 32 * 8;
-    // planar reads: lane = pixel, so one load instruction is 256 contiguous bytes per channel (the channel-last copies
-    // would make every lane fetch its own 128-byte line: 22 us per frame measured, this form ~3)
-#pragma unroll PRE_UNROLL
+#pragma unroll
     for (int c = 0; c < 32; ++c) {
-        const float* gc = g + (size_t)c * n;
-        const float av = gc[ia], bv = gc[ib], cv = gc[ic], dv = gc[id];
+        const float av = cl[ia + c], bv = cl[ib + c], cv = cl[ic + c], dv = cl[id + c];
         ss = fmaf(av, av, ss); hh = fmaf(av, bv, hh); vv = fmaf(av, cv, vv);
         d1 = fmaf(av, dv, d1); d2 = fmaf(bv, cv, d2);
 #pragma unroll
@@ -1140,6 +1065,152 @@ __global__ __launch_bounds__(256) void al_agg_pre_kernel(const float* __restrict
     for (int o = 0; o < 8; ++o) pre[(size_t)o * n + i] = pr[o];
     pre[(size_t)8 * n + i] = ss; pre[(size_t)9 * n + i] = hh; pre[(size_t)10 * n + i] = vv;
     pre[(size_t)11 * n + i] = d1; pre[(size_t)12 * n + i] = d2;
+}
+
+// 1x1 conv (no bias) + SELU of one pixel of the 1/2 level: all 32 outputs from the pixel's 32 inputs, every input loaded up
+// front (r04), weights [ci][32] as wave-uniform scalar loads; ONE chain per output over ci ascending.
+__device__ __forceinline__ void gate32_px(const float* __restrict__ in, int HW, int pc, const float* __restrict__ w, float (&v)[32], float (&acc)[32]) {
+#pragma unroll
+    for (int ci = 0; ci < 32; ++ci) v[ci] = in[(size_t)ci * HW + pc];
+#pragma unroll
+    for (int o = 0; o < 32; ++o) acc[o] = 0.0f;
+#pragma unroll
+    for (int ci = 0; ci < 32; ++ci) {
+        const float* wp = w + ci * 32;
+#pragma unroll
+        for (int o = 0; o < 32; ++o) acc[o] = fmaf(v[ci], wp[o], acc[o]);
+    }
+#pragma unroll
+    for (int o = 0; o < 32; ++o) acc[o] = selu(acc[o]);
+}
+
+// Everything the 1/2 level feeds, from ONE read of x2: the channel-last gate g2cl, the planes pre2, and block3's pooled input
+// (p3 planar and p3cl, al_avgpool's 16-term row-major sum / 16).  A workgroup owns L2_TW x L2_TH pixels - whole 4 x 4 pooling
+// cells, a thread per pixel - and wave 0 gates the 41 halo pixels in a second pass.  The LDS tile ([9][33] pixels x 33 floats)
+// first holds the raw x2 values for the pooling, then the gated ones.
+constexpr int L2_PW = sslam::L2_TW + 1, L2_NP = L2_PW * (sslam::L2_TH + 1), L2_HALO = sslam::L2_TW + sslam::L2_TH + 1;
+static_assert(sslam::L2_TW == 32 && sslam::L2_TH == 8 && sslam::L2_TW * sslam::L2_TH == 256 && L2_HALO <= 64, "a thread per interior pixel, tile rows of 32 lanes, the halo in wave 0");
+__global__ __launch_bounds__(256) void al_level2_kernel(const float* __restrict__ x2 /*[32][H][W]*/, int H, int W, const float* __restrict__ w /*[ci][32]*/,
+                                                        const float* __restrict__ ws0l /*[32][8]*/, float* __restrict__ gcl /*[H W][32]*/,
+                                                        float* __restrict__ pre /*[13][H W]*/, float* __restrict__ p3 /*[32][H/4][W/4]*/,
+                                                        float* __restrict__ p3cl /*[H/4 W/4][32]*/, size_t fs) {
+    __shared__ float cl[L2_NP * 33];
+    const Tile3 b = xcd_band();             // (halo rows and columns are re-read from the L2 that holds them)
+    x2 = fsh(x2, b.z, fs); gcl = fsh(gcl, b.z, fs); pre = fsh(pre, b.z, fs); p3 = fsh(p3, b.z, fs); p3cl = fsh(p3cl, b.z, fs);
+    const int HW = H * W, x0 = b.x * sslam::L2_TW, y0 = b.y * sslam::L2_TH;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5, x = x0 + tx, y = y0 + ty;
+    const int lp = (ty * L2_PW + tx) * 33;
+    float v[32], acc[32];
+    gate32_px(x2, HW, min(y, H - 1) * W + min(x, W - 1), w, v, acc);
+#pragma unroll
+    for (int ci = 0; ci < 32; ++ci) cl[lp + ci] = v[ci];
+    __syncthreads();
+    {   // block3's input: 16 pooling cells x 32 channels, two per thread
+        const int c = threadIdx.x & 31, H3 = H / 4, W3 = W / 4;
+        for (int k = threadIdx.x >> 5; k < 16; k += 8) {
+            const int bx = k & 7, by = k >> 3, X3 = x0 / 4 + bx, Y3 = y0 / 4 + by;
+            if (X3 >= W3 || Y3 >= H3) continue;
+            float u[16];
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) u[4 * a + e] = cl[((by * 4 + a) * L2_PW + bx * 4 + e) * 33 + c];
+            float s = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) s += u[q];
+            const float m = s / 16.0f;
+            p3[(size_t)c * (H3 * W3) + Y3 * W3 + X3] = m;
+            p3cl[(size_t)(Y3 * W3 + X3) * 32 + c] = m;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int o = 0; o < 32; ++o) cl[lp + o] = acc[o];
+    if (threadIdx.x < L2_HALO) {            // the right column, the lower row, the corner: coordinates clamped to the map
+        const int h = threadIdx.x;
+        const int hr = h < sslam::L2_TH ? h : sslam::L2_TH, hc = h < sslam::L2_TH ? sslam::L2_TW : (h - sslam::L2_TH);
+        gate32_px(x2, HW, min(y0 + hr, H - 1) * W + min(x0 + hc, W - 1), w, v, acc);
+        const int hp = (hr * L2_PW + hc) * 33;
+#pragma unroll
+        for (int o = 0; o < 32; ++o) cl[hp + o] = acc[o];
+    }
+    __syncthreads();
+    // g2cl: whole 128-byte lines, a tile row is 4 KB contiguous
+    for (int i = threadIdx.x; i < 256 * 8; i += 256) {
+        const int q = i >> 3, c4 = (i & 7) * 4, r = q >> 5, cc = q & 31;
+        if (x0 + cc < W && y0 + r < H) {
+            const float* s = cl + (r * L2_PW + cc) * 33 + c4;
+            *reinterpret_cast<float4*>(gcl + ((size_t)(y0 + r) * W + x0 + cc) * 32 + c4) = make_float4(s[0], s[1], s[2], s[3]);
+        }
+    }
+    if (x < W && y < H) pre_planes_lds(cl, lp, L2_PW, ws0l, pre, HW, y * W + x);
+}
+
+// The two small levels (1/8: 64 inputs, 1/32: 128) in ONE launch, each taking its role by workgroup index.  A workgroup owns
+// LS_TW x LS_TH level pixels, stages the inputs of its 17 x 5 pixels (halo included, clamped) in LDS as [pixel][CIN], and gates
+// them with a thread per (output channel, pixel group): the thread keeps its channel's CIN weights in registers and walks its
+// pixels, the inputs arriving as 16-byte LDS broadcasts.  The sum is the small-map gate's TWO chains - even ci into a0, odd ci
+// into a1, selu(a0 + a1) - not the 1/2 level's single one.
+constexpr int LS_PW = sslam::LS_TW + 1, LS_NP = LS_PW * (sslam::LS_TH + 1);
+constexpr int LS_SMEM = LS_NP * (128 + 4) + LS_NP * 33;        // floats: the staged inputs at CIN = 128 + the gated tile
+static_assert(sslam::LS_TW * sslam::LS_TH <= 256 && LS_SMEM * 4 <= 64 * 1024, "a thread per interior pixel for the planes; static LDS");
+struct LevelSmall { const float* in; int H, W; const float* w; const float* ws0l; float* gcl; float* pre; int gx; };
+template <int CIN>
+__device__ __forceinline__ void level_small_tile(const LevelSmall& q, int tile, int f, size_t fs, float* __restrict__ smem) {
+    constexpr int XS = CIN + 4;              // (a multiple of four floats: 16-byte reads of a pixel's inputs)
+    float* xs = smem;                        // [LS_NP][XS]
+    float* gs = smem + LS_NP * XS;           // [LS_NP][33]
+    const float* __restrict__ in = fsh(q.in, f, fs);
+    float* __restrict__ gcl = fsh(q.gcl, f, fs);
+    float* __restrict__ pre = fsh(q.pre, f, fs);
+    const int H = q.H, W = q.W, HW = H * W;
+    const int x0 = (tile % q.gx) * sslam::LS_TW, y0 = (tile / q.gx) * sslam::LS_TH;
+    for (int e = threadIdx.x; e < CIN * LS_NP; e += 256) {
+        const int ci = e / LS_NP, pp = e - ci * LS_NP, r = pp / LS_PW, c = pp - r * LS_PW;
+        xs[pp * XS + ci] = in[(size_t)ci * HW + min(y0 + r, H - 1) * W + min(x0 + c, W - 1)];
+    }
+    const int co = threadIdx.x & 31;
+    float wr[CIN];
+#pragma unroll
+    for (int ci = 0; ci < CIN; ++ci) wr[ci] = q.w[ci * 32 + co];
+    __syncthreads();
+#pragma unroll 1
+    for (int pp = threadIdx.x >> 5; pp < LS_NP; pp += 8) {
+        const float4* xp = reinterpret_cast<const float4*>(xs + pp * XS);
+        float a0 = 0.0f, a1 = 0.0f;
+#pragma unroll
+        for (int k = 0; k < CIN / 4; ++k) {
+            const float4 t = xp[k];
+            a0 = fmaf(t.x, wr[4 * k], a0); a1 = fmaf(t.y, wr[4 * k + 1], a1);
+            a0 = fmaf(t.z, wr[4 * k + 2], a0); a1 = fmaf(t.w, wr[4 * k + 3], a1);
+        }
+        const float g = selu(a0 + a1);
+        gs[pp * 33 + co] = g;
+        const int r = pp / LS_PW, c = pp - r * LS_PW;
+        if (r < sslam::LS_TH && c < sslam::LS_TW && y0 + r < H && x0 + c < W) gcl[((size_t)(y0 + r) * W + x0 + c) * 32 + co] = g;
+    }
+    __syncthreads();
+    if (threadIdx.x < sslam::LS_TW * sslam::LS_TH) {
+        const int tx = threadIdx.x % sslam::LS_TW, ty = threadIdx.x / sslam::LS_TW, x = x0 + tx, y = y0 + ty;
+        if (x < W && y < H) pre_planes_lds(gs, (ty * LS_PW + tx) * 33, LS_PW, q.ws0l, pre, HW, y * W + x);
+    }
+}
+__global__ __launch_bounds__(256) void al_level_small_kernel(LevelSmall a, LevelSmall b, int blocks_a, size_t fs) {
+    __shared__ __attribute__((aligned(16))) float smem[LS_SMEM];
+    if ((int)blockIdx.x < blocks_a) level_small_tile<64>(a, (int)blockIdx.x, (int)blockIdx.y, fs, smem);
+    else level_small_tile<128>(b, (int)blockIdx.x - blocks_a, (int)blockIdx.y, fs, smem);
+}
+
+// conv1's weights [16][32] -> [32][16], once at instance creation (al_aggregate_kernel)
+__global__ void al_w1t_kernel(const float* __restrict__ w1, float* __restrict__ w1t) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 16 * 32) w1t[(i % 32) * 16 + i / 32] = w1[i];
+}
+
+// a channel-last level [n][32] -> planar [32][n]: sslam_aliked_debug_read only (buffers 12..14), never the product path
+__global__ void al_cl_to_planar_kernel(const float* __restrict__ cl, float* __restrict__ planar, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 32 * n) planar[i] = cl[(size_t)(i % n) * 32 + i / n];
 }
 
 // contribution of one upsampled level at a full-resolution pixel: s[o] += up(proj[o]), n2 += the quadratic form
@@ -1188,23 +1259,14 @@ AL_AGG_TARGET __global__ __launch_bounds__(256) void al_aggregate_kernel(Pyr P0,
     for (int c = 0; c < 32; ++c) {
         float a = 0.0f;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) a = fmaf(xv[k], P.w1[k * 32 + c], a);
+        for (int k = 0; k < 16; ++k) a = fmaf(xv[k], P.w1t[c * 16 + k], a);
         a = selu_precise(a);
         g1s[threadIdx.x * 33 + c] = a;     // the descriptor head gathers this instead of redoing the 16x32 product
         n2 = fmaf(a, a, n2);
 #pragma unroll
         for (int o = 0; o < 8; ++o) s[o] = fmaf(a, ws0[c * 8 + o], s[o]);
     }
-    const UpTap t2 = up_tap(y, x, P.Hp, P.Wp, 2, P.sy2, P.sx2), t3 = up_tap(y, x, P.Hp, P.Wp, 8, P.sy8, P.sx8),
-                t4 = up_tap(y, x, P.Hp, P.Wp, 32, P.sy32, P.sx32);
-    agg_level(P.pre2, (int)(HW / 4), t2, s, n2);
-    agg_level(P.pre3, (int)(HW / 64), t3, s, n2);
-    agg_level(P.pre4, (int)(HW / 1024), t4, s, n2);
-    if (live) {
-#pragma unroll
-        for (int o = 0; o < 8; ++o) s8[o * HW + pix] = selu_precise(s[o]);
-        rnorm[pix] = 1.0f / fmaxf(sqrtf(n2), 1e-12f);            // F.normalize eps
-    }
+    // r35: the 42 MB of g1cl lines leave as soon as the loop has filled LDS, under the level gathers below
     // (the header's inline functions - __syncthreads, make_float4 - are compiled with the file's target features and would stay
     //  CALLS from a kernel whose features differ: the barrier and the 16-byte store are written with the builtins they wrap)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1217,6 +1279,16 @@ AL_AGG_TARGET __global__ __launch_bounds__(256) void al_aggregate_kernel(Pyr P0,
         const int p = i >> 3, c4 = (i & 7) * 4;
         const f32x4_t v = {g1s[p * 33 + c4], g1s[p * 33 + c4 + 1], g1s[p * 33 + c4 + 2], g1s[p * 33 + c4 + 3]};
         *reinterpret_cast<f32x4_t*>(dst + (size_t)p * 32 + c4) = v;
+    }
+    const UpTap t2 = up_tap(y, x, P.Hp, P.Wp, 2, P.sy2, P.sx2), t3 = up_tap(y, x, P.Hp, P.Wp, 8, P.sy8, P.sx8),
+                t4 = up_tap(y, x, P.Hp, P.Wp, 32, P.sy32, P.sx32);
+    agg_level(P.pre2, (int)(HW / 4), t2, s, n2);
+    agg_level(P.pre3, (int)(HW / 64), t3, s, n2);
+    agg_level(P.pre4, (int)(HW / 1024), t4, s, n2);
+    if (live) {
+#pragma unroll
+        for (int o = 0; o < 8; ++o) s8[o * HW + pix] = selu_precise(s[o]);
+        rnorm[pix] = 1.0f / fmaxf(sqrtf(n2), 1e-12f);            // F.normalize eps
     }
 }
 
@@ -2124,6 +2196,7 @@ struct sslam_aliked {
     _Float16 *b3c1of, *b3c2of, *b4c1of, *b4c2of;                          // the same, split, fragment order (al_offc_wfrag_kernel)
     _Float16 *b3c1f, *b3c2f, *b4c1f, *b4c2f;                              // deformable-conv weights (BN scale folded, + 1 x 1 branch), split, fragment order
     const float *gw1, *gw2, *gw3, *gw4;
+    float* gw1t;                         // gw1 transposed [32][16] (al_w1t_kernel)
     const float *sh0, *sh2, *sh4, *sh6;
     const float *d_ow, *d_ob, *d_w2, *d_b2, *d_sf, *d_agg;
     // workspace
@@ -2201,7 +2274,9 @@ int al_enqueue(sslam_aliked* g, const sslam::ALPlan& p, const FrameIn& srcs, int
                        p.b2_waves, g->b2c1f, g->b2c2f, g->b2c1.a, g->b2c1.b, g->b2db, g->b2c2.a, g->b2c2.b, g->ctrl, fs);
     // block3 at 1/8 (deformable): per layer the offset conv, then sampling + contraction + BN (+ 1 x 1 residual branch) + SELU fused
     const dim3 off3 = dim3(p.off3_gx, p.H3, F), dcn3 = dim3(p.dcn3_gx, p.H3, F);
-    hipLaunchKernelGGL(al_avgpool_kernel, dim3(p.pool3_gx, F), b256, 0, s, g->x2, g->p3, 32, p.H2, p.W2, 4, fs, g->p3cl);
+    // (the 1/2 level in one kernel, from one read of x2: block3's pooled input, the gate g2cl and its pre-aggregation planes)
+    hipLaunchKernelGGL(al_level2_kernel, dim3(p.lvl2_gx, p.lvl2_gy, F), b256, 0, s, g->x2, p.H2, p.W2, g->gw2, g->sh0 + 1 * 32 * 8, g->g2cl,
+                       g->pre2, g->p3, g->p3cl, fs);
     hipLaunchKernelGGL((al_offset_conv_h_kernel<32>), off3, b256, 0, s, g->p3cl, g->off, p.H3, p.W3, g->b3c1of, g->b3c1.ob, p.mo3, g->ctrl, fs);
     hipLaunchKernelGGL((al_dcn_h_kernel<32, 64, 0, DCN3_CS>), dcn3, b256, 0, s, g->p3cl, g->off, nullptr, p.H3, p.W3, g->b3c1f, g->b3c1.b, nullptr, g->t3, g->t3cl, g->ctrl, fs);
     hipLaunchKernelGGL((al_offset_conv_h_kernel<64>), off3, b256, 0, s, g->t3cl, g->off, p.H3, p.W3, g->b3c2of, g->b3c2.ob, p.mo3, g->ctrl, fs);
@@ -2214,17 +2289,15 @@ int al_enqueue(sslam_aliked* g, const sslam::ALPlan& p, const FrameIn& srcs, int
     hipLaunchKernelGGL((al_dcn_h_kernel<64, 128, 0, DCN4_CS>), dcn4, b256, 0, s, g->p4cl, g->off, nullptr, p.H4, p.W4, g->b4c1f, g->b4c1.b, nullptr, g->t4, g->t4cl, g->ctrl, fs);
     hipLaunchKernelGGL((al_offset_conv_h_kernel<128>), off4, b256, 0, s, g->t4cl, g->off, p.H4, p.W4, g->b4c2of, g->b4c2.ob, p.mo4, g->ctrl, fs);
     hipLaunchKernelGGL((al_dcn_h_kernel<128, 128, 64, DCN4_CS>), dcn4, b256, 0, s, g->t4cl, g->off, g->p4cl, p.H4, p.W4, g->b4c2f, g->b4c2.b, g->b4db, g->x4, nullptr, g->ctrl, fs);
-    // gates
-    hipLaunchKernelGGL(al_gate_kernel<32>, dim3(p.gate2_gx, F), b256, 0, s, g->x2, g->g2, p.HW2, g->gw2, g->g2cl, fs);
-    hipLaunchKernelGGL(al_gate_small_kernel, dim3(p.gate34_gx, F), b256, 0, s, GateSmall{g->x3, g->g3, 64, p.HW3, g->gw3, g->g3cl},
-                       GateSmall{g->x4, g->g4, 128, p.HW4, g->gw4, g->g4cl}, p.gate3_gx, fs);
+    // gates + pre-aggregation planes of the two small levels
+    hipLaunchKernelGGL(al_level_small_kernel, dim3(p.lvl34_n, F), b256, 0, s,
+                       LevelSmall{g->x3, p.H3, p.W3, g->gw3, g->sh0 + 2 * 32 * 8, g->g3cl, g->pre3, p.lvl3_gx},
+                       LevelSmall{g->x4, p.H4, p.W4, g->gw4, g->sh0 + 3 * 32 * 8, g->g4cl, g->pre4, p.lvl4_gx}, p.lvl3_n, fs);
     // aggregation + score head
-    Pyr P{g->x1, g->g2, g->g3, g->g4, g->gw1, d.Hp, d.Wp, g->g1cl};
+    Pyr P{g->x1, g->gw1t, d.Hp, d.Wp, g->g1cl};
     P.sy2 = p.sy2; P.sx2 = p.sx2; P.sy8 = p.sy8; P.sx8 = p.sx8; P.sy32 = p.sy32; P.sx32 = p.sx32;
     P.g2cl = g->g2cl; P.g3cl = g->g3cl; P.g4cl = g->g4cl;
     P.pre2 = g->pre2; P.pre3 = g->pre3; P.pre4 = g->pre4;
-    hipLaunchKernelGGL(al_agg_pre_kernel, dim3(p.agg_pre_gx, F), b256, 0, s, g->g2, g->g3, g->g4, g->sh0, g->pre2, g->pre3, g->pre4,
-                       d.Hp, d.Wp, fs);
     hipLaunchKernelGGL(al_aggregate_kernel, dim3(p.pad_gx, d.Hp, F), b256, 0, s, P, g->sh0, g->s8, g->rnorm, fs);
     hipLaunchKernelGGL(al_score_tail_kernel, dim3(p.tail_gx, p.tail_gy, F), dim3(ST_T), 0, s, g->s8, d.Hp, d.Wp, g->sh2, g->sh4, g->sh6,
                        g->score, d.h, d.w, d.pl, d.pt, fs);
@@ -2311,6 +2384,7 @@ int sslam_aliked_create_batched(sslam_ctx* ctx, const float* weights, size_t n_f
         g->b4c1f = A.take<_Float16>((size_t)(9 * 4 + 0) * 4 * 2 * 512); g->b4c2f = A.take<_Float16>((size_t)(9 * 8 + 4) * 4 * 2 * 512);
         g->b3c1of = A.take<_Float16>(18 * 2 * 512); g->b3c2of = A.take<_Float16>(36 * 2 * 512); g->b4c1of = A.take<_Float16>(36 * 2 * 512); g->b4c2of = A.take<_Float16>(72 * 2 * 512);
         g->gk = A.take<float>(64);
+        g->gw1t = A.take<float>(32 * 16);
         g->range_sticky = A.take<int>(4);
     };
     // one workspace block per frame of a batch (frame f's copy of a buffer = frame 0's + f * g->fs bytes)
@@ -2369,6 +2443,7 @@ int sslam_aliked_create_batched(sslam_ctx* ctx, const float* weights, size_t n_f
         hipLaunchKernelGGL(al_offc_wfrag_kernel<64>, dim3(sslam::cdiv(36 * 512, 256)), dim3(256), 0, s, g->b3c2.ow, g->b3c2of, g->range_sticky);
         hipLaunchKernelGGL(al_offc_wfrag_kernel<64>, dim3(sslam::cdiv(36 * 512, 256)), dim3(256), 0, s, g->b4c1.ow, g->b4c1of, g->range_sticky);
         hipLaunchKernelGGL(al_offc_wfrag_kernel<128>, dim3(sslam::cdiv(72 * 512, 256)), dim3(256), 0, s, g->b4c2.ow, g->b4c2of, g->range_sticky);
+        hipLaunchKernelGGL(al_w1t_kernel, dim3(2), dim3(256), 0, s, g->gw1, g->gw1t);
         int wflag = 0;
         SSLAM_HIP_CHECK(hipMemcpyAsync(&wflag, g->range_sticky, sizeof(int), hipMemcpyDeviceToHost, s));
         SSLAM_HIP_CHECK(hipStreamSynchronize(s));
@@ -2493,7 +2568,7 @@ int sslam_aliked_extract_host(sslam_aliked* g, const uint8_t* img, int H, int W,
 
 /* Test hook.  which: 0 = score map [h][w], 1 = kp_index [n] (int32), 2 = dims {h,w,Hp,Wp,pl,pt,n_cand,n_kp},
  * 3 = x1 [16][Hp][Wp], 4 = x2, 5 = x3, 6 = x4, 7 = img [3][Hp][Wp], 8 = nms [h][w], 9 = kp_norm [n][2],
- * 10 = g1 channel-last [Hp][Wp][32], 11 = rnorm [Hp][Wp], 12..14 = g2..g4 planar, 15..17 = pre2..pre4 [13][level pixels],
+ * 10 = g1 channel-last [Hp][Wp][32], 11 = rnorm [Hp][Wp], 12..14 = g2..g4 planar (transposed here from the channel-last copies), 15..17 = pre2..pre4 [13][level pixels],
  * 18 = s8 [8][Hp][Wp], 19 = pos [n][16][2], 20 = patch [n][1152].  Frame 0 of a batch; all read-only. */
 int sslam_aliked_debug_read(sslam_aliked* g, int which, void* dst, size_t bytes) {
     SSLAM_REQUIRE(g && dst, "sslam_aliked_debug_read: NULL argument");
@@ -2524,9 +2599,19 @@ int sslam_aliked_debug_read(sslam_aliked* g, int which, void* dst, size_t bytes)
         case 9: src = g->kp_norm; cap = (size_t)g->max_kpts * 8; break;
         case 10: src = g->g1cl; cap = e.g1cl * 4; break;           // (r04: the aggregation's outputs and the gated levels, for determinism checks)
         case 11: src = g->rnorm; cap = e.rnorm * 4; break;
-        case 12: src = g->g2; cap = e.g2 * 4; break;
-        case 13: src = g->g3; cap = e.g3 * 4; break;
-        case 14: src = g->g4; cap = e.g4 * 4; break;
+        case 12: case 13: case 14: {
+            // the planar levels are no longer written by the extraction: filled here, on request, from the channel-last copies
+            const int lv = which - 12, S = lv == 0 ? 2 : lv == 1 ? 8 : 32, n = (d.Hp / S) * (d.Wp / S);
+            const float* cl = lv == 0 ? g->g2cl : lv == 1 ? g->g3cl : g->g4cl;
+            float* planar = lv == 0 ? g->g2 : lv == 1 ? g->g3 : g->g4;
+            cap = (lv == 0 ? e.g2 : lv == 1 ? e.g3 : e.g4) * 4;
+            SSLAM_REQUIRE(n > 0 && d.Hp <= g->Hp_cap && d.Wp <= g->Wp_cap, "sslam_aliked_debug_read: no admitted frame to read level %d of", lv + 2);
+            hipLaunchKernelGGL(al_cl_to_planar_kernel, dim3(sslam::cdiv(32 * n, 256)), dim3(256), 0, g->ctx->stream, cl, planar, n);
+            SSLAM_HIP_CHECK(hipGetLastError());
+            SSLAM_HIP_CHECK(hipStreamSynchronize(g->ctx->stream));
+            src = planar;
+            break;
+        }
         case 15: src = g->pre2; cap = e.pre2 * 4; break;
         case 16: src = g->pre3; cap = e.pre3 * 4; break;
         case 17: src = g->pre4; cap = e.pre4 * 4; break;
