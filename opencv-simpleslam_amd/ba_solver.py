@@ -80,21 +80,25 @@ class _Evaluator:
         self.p = prob
         self.ctx = ctx
         n = len(prob.obs_pose)
+        # the kernel's types, whatever the caller's arrays hold (as solve_device casts them); kept for every call
+        self.obs_pose = np.ascontiguousarray(prob.obs_pose, np.int32)
+        self.obs_point = np.ascontiguousarray(prob.obs_point, np.int32)
+        self.uv = np.ascontiguousarray(prob.obs_uv, np.float64)
+        self.intr = np.ascontiguousarray(prob.intr, np.float64)
         self.r = np.empty((n, 2))
         self.Jq = np.empty((n, 2, 4))
         self.Jt = np.empty((n, 2, 3))
         self.JX = np.empty((n, 2, 3))
 
     def __call__(self, q, t, X, jac: bool):
-        p = self.p
         L = _native.lib()
-        q = np.ascontiguousarray(q)
-        t = np.ascontiguousarray(t)
-        X = np.ascontiguousarray(X)
+        q = np.ascontiguousarray(q, np.float64)
+        t = np.ascontiguousarray(t, np.float64)
+        X = np.ascontiguousarray(X, np.float64)
         P = _native.ptr
         _native.check(L.sslam_ba_residual_jacobian_host(
-            self.ctx.handle, len(p.obs_pose), P(p.obs_pose), P(p.obs_point), P(p.obs_uv),
-            len(q), P(q), P(t), len(X), P(X), P(p.intr), P(self.r),
+            self.ctx.handle, len(self.obs_pose), P(self.obs_pose), P(self.obs_point), P(self.uv),
+            len(q), P(q), P(t), len(X), P(X), P(self.intr), P(self.r),
             P(self.Jq) if jac else None, P(self.Jt) if jac else None, P(self.JX) if jac else None),
             "sslam_ba_residual_jacobian_host")
         return self.r

@@ -51,7 +51,7 @@ def _check_image(img):
         raise ValueError(f"{Cn} channels (want 1, 3 or 4)")
     if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
         raise ValueError(f"image size {W}x{H} outside 1..{MAX_SIDE}")
-    return img, H, W, Cn
+    return np.ascontiguousarray(img), H, W, Cn
 
 
 def _check_window(winSize, maxLevel):
@@ -93,7 +93,7 @@ def bgr_to_gray(img, ctx=None):
     ctx = ctx or _native.default_context()
     out = np.empty((H, W), np.uint8)
     P = _native.ptr
-    _native.check(_native.lib().sslam_klt_gray_host(ctx.handle, P(np.ascontiguousarray(img)), H, W, Cn, P(out)), "sslam_klt_gray_host")
+    _native.check(_native.lib().sslam_klt_gray_host(ctx.handle, P(img), H, W, Cn, P(out)), "sslam_klt_gray_host")
     return out
 
 
@@ -136,10 +136,10 @@ class _Instance:
             raise ValueError(f"frame size {W}x{H} is not the tracker's {self.size[0]}x{self.size[1]}")
 
     def push(self, img):
-        img, H, W, Cn = _check_image(img)
+        img, H, W, Cn = _check_image(img)                # (a view's copy must live across the call: `img` holds it)
         self._check_frame(H, W)
         self._alive()
-        _native.check(_native.lib().sslam_klt_push_host(self.handle, _native.ptr(np.ascontiguousarray(img)), H, W, Cn), "sslam_klt_push_host")
+        _native.check(_native.lib().sslam_klt_push_host(self.handle, _native.ptr(img), H, W, Cn), "sslam_klt_push_host")
         self.pushes += 1
 
     def push_dev(self, img_dev, H, W, Cn):

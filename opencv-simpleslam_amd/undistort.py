@@ -193,9 +193,9 @@ class Undistorter:
         self._init_buffers(ctx)
         h = C.c_void_p()
         P = _native.ptr
+        nk = np.ascontiguousarray(new_K, np.float64).reshape(9)      # (a copy must live across the call)
         _native.check(_native.lib().sslam_undistort_create(self.ctx.handle, P(K.reshape(9)), P(d), int(d.size),
-                                                           P(Rm.reshape(9)) if Rm is not None else None,
-                                                           P(np.ascontiguousarray(new_K).reshape(9)), W, H, C.byref(h)),
+                                                           P(Rm.reshape(9)) if Rm is not None else None, P(nk), W, H, C.byref(h)),
                       "sslam_undistort_create")
         self.handle = h
 
@@ -218,8 +218,8 @@ class Undistorter:
         self._init_buffers(ctx)
         h = C.c_void_p()
         P = _native.ptr
-        _native.check(_native.lib().sslam_undistort_create_from_maps(self.ctx.handle, P(np.ascontiguousarray(mapx)),
-                                                                     P(np.ascontiguousarray(mapy)), W, H, C.byref(h)),
+        mx, my = np.ascontiguousarray(mapx), np.ascontiguousarray(mapy)      # (a view's copy must live across the call)
+        _native.check(_native.lib().sslam_undistort_create_from_maps(self.ctx.handle, P(mx), P(my), W, H, C.byref(h)),
                       "sslam_undistort_create_from_maps")
         self.handle = h
         return self

@@ -24,9 +24,33 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, s), f"libsslam_hip.so does not export {s}"
 
 
+def _accepted(native, p):
+    """the ctypes types that may stand for a header parameter (or a return type, whose name is empty)"""
+    import ctypes as C
+    scalar = {"int": C.c_int, "size_t": C.c_size_t, "int64": C.c_int64, "float": C.c_float, "double": C.c_double}
+    if p.cls in scalar:
+        return (scalar[p.cls],)
+    if p.cls == "pointer-to-pointer":
+        return (C.c_void_p, native.c_void_pp) if not p.const else (C.c_void_p,)
+    if p.elem == "char":
+        return (C.c_char_p,)
+    return {"int32_t": (C.c_void_p, native.c_int_p), "float": (C.c_void_p, native.c_float_p)}.get(p.elem, (C.c_void_p,))
+
+
 def test_binding_matches_header():
+    import binding_probe
     native = load_pkg("_native")
     assert sorted(native.declared_symbols()) == _header_symbols()
+    model, sigs = binding_probe.header_model(), native._signatures()
+    assert sorted(model) == _header_symbols()
+    for name, proto in model.items():
+        res, args = sigs[name]
+        ret = binding_probe.Param("", proto.ret, proto.ret_elem, True)
+        assert res in _accepted(native, ret), f"{name}: returns {proto.ret} in the header, the binding says {res.__name__}"
+        assert len(args) == len(proto.params), f"{name}: {len(proto.params)} parameters in the header, {len(args)} argtypes"
+        for i, (p, t) in enumerate(zip(proto.params, args)):
+            assert t in _accepted(native, p), (f"{name}: parameter {i} `{p.name}` is {p.cls}{' of ' + p.elem if p.elem else ''} in the header, "
+                                               f"the binding says {t.__name__}")
 
 
 def test_abi_version_and_error_string():
